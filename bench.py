@@ -8,14 +8,15 @@ LLaVA-1.5-7B, bf16, B=1, one synthetic 336x336 image, prompt = 35 system tokens 
 (N = 631 -> N' = 170), vision_keep_rate=0.2.  tokens/step = N + T_new (the reference's own accounting counts all
 576 image tokens: llava/dynamic_eval/bench_test/dynamic_llava_long_text_mem.py:317-323).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]    (the headline: set-up, W warm-up steps, K timed steps, one line)
+    python bench.py --gpus 1 --steps K --warmup W --full                  (+ everything else it measures and checks, after the timed steps)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
     python bench.py --gpus N ...        (no launcher: bench.py starts the N ranks itself through torch.distributed.run)
 
 N > 1: weak scaling, one identical request per rank (weights replicated), one RCCL all-gather (a single
 all_gather_into_tensor carrying the last-token logits + generated ids + their shapes) per step, no collective in the decode loop.  The ranks' results must be identical (FATAL otherwise).
-After the timed region an N > 1 run also executes BASELINE configs[3] once (32 ragged requests per rank, one all-gather) and checks
+With --full, after the timed region an N > 1 run also executes BASELINE configs[3] once (32 ragged requests per rank, one all-gather) and checks
 the gathered rows against a re-run of another rank's chunk.  Rank 0 prints ONE JSON line.
 
 The output-text predictor is random-init here: its keep/evict bit would saturate one way, so its final bias is calibrated on the
@@ -63,13 +64,19 @@ def parse():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--new-tokens", type=int, default=64)
     ap.add_argument("--layers", type=int, default=32, help="debug only: fewer decoder layers => the JSON is marked INVALID")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ref-gpu", action="store_true")
+    ap.add_argument("--full", action="store_true", help="after the headline, also measure and check everything else: phase split, per-kernel rooflines, the "
+                    "reference-path and CPU baselines, the configs[2] / configs[4] legs and measured ceilings (N = 1), the configs[3] leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step returned (generated ids, prefill last-token logits, KV lengths) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-ref-gpu", action="store_true", help="with --full: skip the reference-path baseline")
     ap.add_argument("--no-graph", action="store_true")
     ap.add_argument("--predictor-gain", type=float, default=50.0, help="'trained-like' predictor scaling (no score ties); 1.0 = plain random init")
     ap.add_argument("--no-calibrate", action="store_true", help="leave the random-init output-text predictor as is (it then keeps or evicts everything)")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the untimed configs[2] / configs[4] legs and the measured ceilings (N = 1 only; they add ~2 minutes)")
-    return ap.parse_args()
+    ap.add_argument("--no-extra-legs", action="store_true", help="with --full: skip the untimed configs[2] / configs[4] legs and the measured ceilings (N = 1 only; they add ~2 minutes)")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def make_inputs(cfg, device, dtype):
@@ -78,6 +85,19 @@ def make_inputs(cfg, device, dtype):
     prompt = torch.cat([torch.tensor([1]), ids[: N_SYS - 1], torch.tensor([-200]), ids[N_SYS:]]).long()[None]
     images = torch.randn((1, 3, 336, 336), generator=g).to(dtype)
     return prompt.to(device), images.to(device)
+
+
+def dump_outputs(out_dir, ids, model):
+    """What a caller of the timed step receives from its last call: the generated ids ([B, T_new], as generate() returns them), the fp32
+    logits of the prompt's last token and the KV lengths the cache ends at ([2, B]: layers before / from the sparse layer).  float64 for the integers
+    (exact), float32 for the logits."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"generated_ids": ids.cpu().double().numpy(), "prefill_last_logits": model.last_prefill_logits.cpu().float().numpy(),
+              "kv_lens": model.last_cache.lens.cpu().double().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
 
 
 def event_time_ms(fn, iters, warmup=3):
@@ -840,8 +860,9 @@ def _main(args, partial):
                    "note": "each rank's own time for the K steps (its collectives included), before the closing barrier; `ms_per_step` is the max over ranks of the barrier-closed time"}
     partial.update(ms_per_step=round(elapsed * 1e3 / args.steps, 3), value_if_valid=round(world * (n_prompt + T_new) * args.steps / elapsed, 2))
     model.check_device_errors()  # a launch with in-kernel hand-offs that gave up would have poisoned its output: never report such a run
-    end_lens = model.last_cache.lens.cpu().tolist()  # KV lengths at the end of a full step (before the pooled slab is reset)
-    dp_consistent = None
+    if args.dump_outputs and rank == 0:  # what the last timed step computed, before any other call touches the model (ranks hold identical requests)
+        dump_outputs(args.dump_outputs, out, model)
+    dp_consistent, lg_diff = None, None
     c3 = None
     if world > 1:  # identical requests on every rank: the gathered token ids must be identical -- FATAL otherwise (a DP run whose ranks disagree
         # measured nothing); the gathered prefill logits must agree to the last bit too, or -- if a device's library GEMM picked another
@@ -856,12 +877,37 @@ def _main(args, partial):
             if rank == 0:  # every rank holds the same gathered tensors: one line, from rank 0
                 raise BenchAbort("data-parallel ranks produced different results for identical requests", ids_equal=ids_same, max_logit_diff=lg_diff, logit_magnitude=lg_mag, per_rank=per_rank)
             sys.exit(2)
-        c3 = configs3_leg(model, cfg, dd, rank, world, device, dtype)
+        if args.full:
+            c3 = configs3_leg(model, cfg, dd, rank, world, device, dtype)
 
     if rank != 0:
         return
     ms_per_step = elapsed * 1e3 / args.steps
     value = world * (n_prompt + T_new) * args.steps / elapsed
+    res = {
+        "metric": METRIC,
+        "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic (random-init LLaVA-1.5-7B + CLIP ViT-L/14-336 weights, randn 336x336 image, random token ids)",
+        "config": {"workload": "BASELINE configs[1]: LLaVA-1.5-7B bf16, B=1 per GPU, 1 image, prompt 35+576+20=631 tokens (170 after layer 2), "
+                               f"vision_keep_rate=0.2, output-text KV eviction on, greedy {T_new} new tokens; step = CLIP+projector+prefill+decode",
+                   "tokens_per_step_per_gpu": n_prompt + T_new, "parallelism": f"dp{world}", "dist": dist_view, "dp_rows_identical": dp_consistent, "dp_max_abs_logit_diff": (lg_diff if world > 1 else None), "rank_spread": rank_spread, "hip_graph_decode": model.use_hip_graph,
+                   "predictor_gain": args.predictor_gain, "text_predictor_calibrated_keep_fraction": calib, "knobs": model.knobs(),
+                   "parity_note": "ids / kept sets / KV lengths bit-exact vs the oracle; logits: 1e-3 asserted literally in fp32, bf16 held to the reference's own "
+                                  "eager-bf16 noise class against an fp32 truth (DESIGN.md section 5)"},
+    }
+    if c3 is not None:
+        res["configs3"] = c3
+    if args.layers != 32:
+        res["INVALID"] = f"debug run with {args.layers} layers"
+    if args.full:  # everything else the benchmark reports, measured after the headline and outside its timed region
+        full_report(res, args, model, cfg, prompt, images, device, dtype, world, n_prompt, T_new, ms_per_step, value)
+    print(json.dumps(res))
+
+
+def full_report(res, args, model, cfg, prompt, images, device, dtype, world, n_prompt, T_new, ms_per_step, value):
+    """`--full`: adds to the result line the phase split, the per-kernel rooflines, the reference-path and CPU baselines and (N = 1) the
+    configs[2] / configs[4] legs and the measured ceilings.  Runs after the timed steps; none of it enters `value` or `ms_per_step`."""
     # ---- phase split (outside the timed region) ----
     out = model.generate(prompt, images=images, max_new_tokens=T_new, do_sample=False, num_beams=1, use_cache=True, eos_token_id=None)  # fresh run: end_lens of a step
     end_lens = model.last_cache.lens.cpu().tolist()
@@ -925,17 +971,7 @@ def _main(args, partial):
              "frac": round(step_bytes / dec_ms / 1e6 / HBM_PEAK_GBS, 4),
              "note": "all weights streamed by one decode step + the K/V rows its attention reads (at the final lengths), over decode_ms_per_token of the timed generate() "
                      "calls: includes every launch of the step's graph, launch boundaries and the host loop"}
-    res = {
-        "metric": METRIC,
-        "value": round(value, 2), "unit": "tokens/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "bf16", "data": "synthetic (random-init LLaVA-1.5-7B + CLIP ViT-L/14-336 weights, randn 336x336 image, random token ids)",
-        "config": {"workload": "BASELINE configs[1]: LLaVA-1.5-7B bf16, B=1 per GPU, 1 image, prompt 35+576+20=631 tokens (170 after layer 2), "
-                               f"vision_keep_rate=0.2, output-text KV eviction on, greedy {T_new} new tokens; step = CLIP+projector+prefill+decode",
-                   "tokens_per_step_per_gpu": n_prompt + T_new, "parallelism": f"dp{world}", "dist": dist_view, "dp_rows_identical": dp_consistent, "dp_max_abs_logit_diff": (lg_diff if world > 1 else None), "rank_spread": rank_spread, "hip_graph_decode": model.use_hip_graph,
-                   "predictor_gain": args.predictor_gain, "text_predictor_calibrated_keep_fraction": calib, "knobs": model.knobs(),
-                   "parity_note": "ids / kept sets / KV lengths bit-exact vs the oracle; logits: 1e-3 asserted literally in fp32, bf16 held to the reference's own "
-                                  "eager-bf16 noise class against an fp32 truth (DESIGN.md section 5)"},
+    res.update({
         "phases": {"prefill_ms": round(pre_ms, 3), "clip_projector_ms": round(clip_ms, 3), "clip_projector_graph_ms": (None if clip_graph_ms is None else round(clip_graph_ms, 3)), "decode_ms_per_token": round(dec_ms, 4),
                    "prefill_tokens_per_s": round(n_prompt / pre_ms * 1e3, 1), "decode_tokens_per_s": round(1e3 / dec_ms, 1),
                    "kv_len_full": t_full, "kv_len_sparse": t_sparse,
@@ -948,11 +984,7 @@ def _main(args, partial):
                      "bytes_per_step": roof_main["bytes_per_step"], "us_per_step": roof_main["us_per_step"], "whole_step": whole,
                      "note": "averaged over the 129 dl_gemv launches of one decode step replayed as one hipGraph between HIP events on the launch stream (includes inter-kernel gaps); the north_star's sparse-attention kernel is the first entry of roofline_kernels; in the product step the q|k|v launches of the single-split layers also carry that layer's attention workgroups (dl_gemv_qkv_attn) and one gate|up launch the text predictor (dl_gemv_gu_tp): same streaming body, same bytes"},
         "roofline_kernels": extra,
-    }
-    if c3 is not None:
-        res["configs3"] = c3
-    if args.layers != 32:
-        res["INVALID"] = f"debug run with {args.layers} layers"
+    })
     if world == 1 and not args.no_ref_gpu:
         try:
             res["ref_gpu_path"] = ref_gpu_path(model, prompt, images, T_new)
@@ -980,7 +1012,6 @@ def _main(args, partial):
             m = res["measured_ceilings"]["hbm_copy_GBps"]
             res["roofline"]["frac_of_measured_copy"] = round(res["roofline"]["achieved"] / m, 4)
             res["roofline"]["whole_step"]["frac_of_measured_copy"] = round(whole["achieved"] / m, 4)
-    print(json.dumps(res))
 
 
 if __name__ == "__main__":

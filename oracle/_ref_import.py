@@ -1,8 +1,8 @@
 """TEST INFRASTRUCTURE ONLY -- loads the *reference* (Osilly/dynamic_llava) from /root/reference.
 
 Only usable in the build container (the reference never travels to the GPU box). Used by
-`oracle/make_golden.py` to generate the committed golden vectors under tests/golden/ and by
-`tests/test_oracle_vs_reference.py` (skipped when /root/reference is absent).
+`oracle/make_golden.py`, `oracle/make_golden_train.py` and `oracle/make_golden_vs_reference.py` to generate the committed golden
+vectors under tests/golden/; no test imports it.
 
 Shims: transformers 5.x removed `is_torch_fx_available` (used at
 llava/model/language_model/dynamic_modeling_llama.py:53,75-79) and folds rope_theta / rope_scaling

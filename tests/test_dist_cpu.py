@@ -171,3 +171,33 @@ def test_bench_refuses_more_ranks_than_gpus_with_a_json_line():
     assert r.returncode == 2, (r.returncode, r.stderr[-1500:])
     d = json.loads(r.stdout.strip().splitlines()[-1])
     assert d["value"] is None and "visible GPU" in d["error"] and d["detail"]["gpus"] == 2 and d["partial"]["n_gpus"] == 2
+
+
+def test_bench_options_and_output_dump(tmp_path, monkeypatch):
+    """bench.py's plain run is the headline only (`--full` adds the rest), `--steps` must name at least one timed step, and `--dump-outputs`
+    writes what the last timed step returned as float .npy files (integers exactly, in float64)."""
+    import types
+
+    import numpy as np
+
+    sys.path.insert(0, ROOT)
+    import bench
+
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    a = bench.parse()
+    assert a.steps == 3 and a.warmup == 1 and a.full is False and a.dump_outputs is None
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", str(tmp_path / "o")])
+    a = bench.parse()
+    assert a.full is True and a.dump_outputs == str(tmp_path / "o")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+    ids = torch.tensor([[1, 5, 31999, 7]])
+    logits = torch.randn(1, 32000)
+    lens = torch.tensor([[12], [9]], dtype=torch.int32)
+    model = types.SimpleNamespace(last_prefill_logits=logits, last_cache=types.SimpleNamespace(lens=lens))
+    bench.dump_outputs(str(tmp_path / "o"), ids, model)
+    got = {n: np.load(tmp_path / "o" / f"{n}.npy") for n in ("generated_ids", "prefill_last_logits", "kv_lens")}
+    assert got["generated_ids"].dtype == np.float64 and got["generated_ids"].tolist() == ids.tolist()
+    assert got["prefill_last_logits"].dtype == np.float32 and np.array_equal(got["prefill_last_logits"], logits.numpy())
+    assert got["kv_lens"].dtype == np.float64 and got["kv_lens"].tolist() == lens.tolist()

@@ -157,7 +157,7 @@ def test_bench_self_launches_two_ranks_without_torchrun():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--layers", "4", "--new-tokens", "8",
-                        "--no-cpu-baseline", "--no-ref-gpu"], capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-ref-gpu"], capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -178,7 +178,7 @@ def test_bench_self_launches_eight_ranks_on_one_gpu():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--steps", "1", "--warmup", "1", "--layers", "2", "--new-tokens", "4",
-                        "--no-cpu-baseline", "--no-ref-gpu"], capture_output=True, text=True, env=env, timeout=2400, cwd=ROOT)
+                        "--full", "--no-cpu-baseline", "--no-ref-gpu"], capture_output=True, text=True, env=env, timeout=2400, cwd=ROOT)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     res = json.loads(line)
@@ -189,3 +189,31 @@ def test_bench_self_launches_eight_ranks_on_one_gpu():
     c3 = res["configs3"]
     assert c3["gathered_rows"] == 256 and c3["rows_per_rank"] == [32] * 8 and c3["collectives_per_batch"] == 1
     assert c3["dp_equals_rerun_of_last_rank"] is True, c3
+
+
+def test_bench_plain_run_is_the_headline_and_its_outputs_repeat(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (no `--full`): one line with the headline keys and none of the `--full` legs, K timed
+    steps, and the last step's outputs under DIR.  Two runs with the same arguments dump identical arrays (same seeded inputs, same results).
+    Two decoder layers keep it short (the line is marked INVALID by bench.py itself)."""
+    import json
+    import subprocess
+
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR", "DL_FORCE_DEVICE")}
+    dumps = []
+    for run in range(2):
+        d = tmp_path / f"run{run}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--layers", "2", "--new-tokens", "6",
+                            "--dump-outputs", str(d)], capture_output=True, text=True, env=env, timeout=900, cwd=ROOT)
+        assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
+        res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert res["steps"] == 3 and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+        assert res["unit"] == "tokens/s" and res["higher_is_better"] is True and res["dtype"] == "bf16"
+        assert not {"phases", "roofline", "roofline_kernels", "ref_gpu_path", "cpu_baseline", "measured_ceilings", "configs2", "configs4"} & set(res)
+        dumps.append({n: np.load(d / f"{n}.npy") for n in ("generated_ids", "prefill_last_logits", "kv_lens")})
+    a, b = dumps
+    assert a["generated_ids"].shape == (1, 6) and a["kv_lens"].shape[-1] == 1, (a["generated_ids"].shape, a["kv_lens"].shape)
+    assert a["prefill_last_logits"].dtype == np.float32 and np.isfinite(a["prefill_last_logits"]).all()
+    for n in a:
+        np.testing.assert_array_equal(a[n], b[n], err_msg=n)

@@ -1,22 +1,20 @@
-"""CPU, build container only: the oracle (oracle/ref_cpu.py) against the reference RUN LIVE from /root/reference on seeds and
-shapes that are NOT among the committed golden vectors.  Skipped where the reference tree is absent (the GPU box): there the
-committed tests/golden/*.npz (produced by the same code path, oracle/make_golden.py) pin the oracle instead."""
+"""CPU: the oracle (oracle/ref_cpu.py) against outputs of the reference on seeds and shapes that are NOT among the golden cases of
+oracle/make_golden.py.  The reference's outputs were recorded by running it (oracle/make_golden_vs_reference.py) into
+tests/golden/oracle_vs_reference.npz; the inputs are regenerated here from the same seeds, so nothing outside the repository is read."""
+import json
+import os
+
 import numpy as np
 import pytest
 import torch
 
-from oracle import fixtures as fx
-from oracle._ref_import import reference_available
+from oracle.make_golden_vs_reference import LOOP_CASES, PREP_CASES, loop_inputs, loop_key, prep_inputs, prep_key
 from oracle.ref_cpu import Oracle
-
-pytestmark = pytest.mark.skipif(not reference_available(), reason="/root/reference is not present (reference code never travels)")
 
 
 @pytest.fixture(scope="module")
-def dll():
-    from oracle._ref_import import import_reference
-
-    return import_reference()
+def recorded(golden_dir):
+    return np.load(os.path.join(golden_dir, "oracle_vs_reference.npz"))
 
 
 @pytest.mark.parametrize(
@@ -27,16 +25,12 @@ def dll():
         (torch.float32, dict(vision_keep_rate=0.5, use_instruct_predictor=True), 3, 15, 3, 9),
     ],
 )
-def test_oracle_equals_live_reference(dll, dtype, sparse, n_sys, n_q, steps, seed):
-    from oracle.make_golden import run_reference
-
-    cfg = fx.tiny_config(**sparse)
-    sd = fx.make_state_dict(cfg, seed=seed, predictor_gain=50.0)
-    clip = fx.build_clip(cfg, seed=seed + 1)
-    ids = fx.make_prompt(cfg, n_sys, n_q, seed=seed)[None]
-    images = fx.make_images(cfg, 1, seed=seed)
-    forced = fx.make_forced_tokens(cfg, steps + 1, 1, seed=seed)
-    ref = run_reference(dll, cfg, sd, clip, dtype, ids, images, steps, forced)
+def test_oracle_equals_live_reference(recorded, dtype, sparse, n_sys, n_q, steps, seed):
+    case = (dtype, sparse, n_sys, n_q, steps, seed)
+    cfg, sd, clip, ids, images, forced = loop_inputs(*case)
+    k = loop_key(LOOP_CASES.index(case))
+    ref = {name: recorded[f"{k}_{name}"] for name in ("step_logits", "position_ids", "len_last", "len_first")}
+    assert ref["step_logits"].shape[0] == steps + 1
     o = Oracle(cfg, sd, dtype, clip=clip, tie_break="torch")  # argsort called exactly as the reference does (DML:1902-1908): ties included
     pkv, cur = None, ids
     with torch.no_grad():
@@ -51,34 +45,20 @@ def test_oracle_equals_live_reference(dll, dtype, sparse, n_sys, n_q, steps, see
 
 
 @pytest.mark.parametrize("side,tmax", [("right", None), ("left", None), ("right", 42), ("left", 42)])
-def test_oracle_prepare_inputs_padding_and_truncation_equal_live_reference(dll, side, tmax):
+def test_oracle_prepare_inputs_padding_and_truncation_equal_live_reference(recorded, side, tmax):
     """ARCH:493-579 -- tokenizer_model_max_length truncation and left / right padding of a ragged batch: embeddings, attention mask,
     position ids and the (shifted / clamped) segment dicts, bit for bit against the reference."""
-    from oracle.make_golden import build_reference_model
-
-    cfg = fx.tiny_config()
-    sd = fx.make_state_dict(cfg, seed=5, predictor_gain=50.0)
-    clip = fx.build_clip(cfg, seed=6)
-    prompts = [fx.make_prompt(cfg, 4, 9, seed=1), fx.make_prompt(cfg, 2, 5, seed=2)]
-    W = max(p.shape[0] for p in prompts)
-    ids = torch.zeros(2, W, dtype=torch.long)
-    am = torch.zeros(2, W, dtype=torch.bool)
-    for b, p in enumerate(prompts):
-        ids[b, : p.shape[0]] = p
-        am[b, : p.shape[0]] = True
-    images = fx.make_images(cfg, 2, seed=3)
-    model = build_reference_model(dll, cfg, sd, clip, torch.float32)
-    model.config.tokenizer_padding_side = side
-    model.config.tokenizer_model_max_length = tmax
-    pos = torch.arange(W)[None].repeat(2, 1)
-    with torch.inference_mode():
-        (_, r_pos, r_am, _, r_emb, _), (r_idx,) = model.prepare_inputs_labels_for_multimodal(ids, pos, am, None, None, images)
+    assert (side, tmax) in PREP_CASES
+    cfg, sd, clip, ids, am, pos, images = prep_inputs()
+    k = prep_key(side, tmax)
+    r_emb, r_am, r_pos = recorded[f"{k}_emb"], recorded[f"{k}_am"], recorded[f"{k}_pos"]
+    r_idx = json.loads(str(recorded[f"{k}_idx"]))
     cfg.tokenizer_padding_side = side
     cfg.tokenizer_model_max_length = tmax
     o = Oracle(cfg, sd, torch.float32, clip=clip)
     with torch.no_grad():
         (_, o_pos, o_am, _, o_emb, _), (o_idx,) = o.prepare_inputs_labels_for_multimodal(ids, pos, am, None, None, images)
-    np.testing.assert_array_equal(o_emb.numpy(), r_emb.numpy())
-    np.testing.assert_array_equal(o_am.numpy(), r_am.numpy())
-    np.testing.assert_array_equal(o_pos.numpy(), r_pos.numpy())
-    assert [{k: list(v) for k, v in d.items()} for d in o_idx] == [{k: [int(v[0]), int(v[1])] for k, v in d.items()} for d in r_idx]
+    np.testing.assert_array_equal(o_emb.numpy(), r_emb)
+    np.testing.assert_array_equal(o_am.numpy(), r_am)
+    np.testing.assert_array_equal(o_pos.numpy(), r_pos)
+    assert [{k: list(v) for k, v in d.items()} for d in o_idx] == r_idx
