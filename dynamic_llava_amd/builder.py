@@ -85,8 +85,13 @@ def _load_checkpoint_tensors(model_path):
 
 
 @torch.no_grad()
-def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bit=False, load_4bit=False, device_map="auto", device="cuda", use_flash_attn=False, torch_dtype=None, **kwargs):
-    """dynamic_llava_builder.py:35-249.  Returns (tokenizer, model, image_processor, context_len)."""
+def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bit=False, load_4bit=False, device_map="auto", device="cuda", use_flash_attn=False, torch_dtype=None,
+                          decode_weight_format=None, **kwargs):
+    """dynamic_llava_builder.py:35-249.  Returns (tokenizer, model, image_processor, context_len).
+    decode_weight_format: None or "mxfp8" (model.set_decode_weight_format: the decoder's projection weights become their MXFP8 values W' in the model dtype and
+    the small-batch decode step streams the FP8 codes).  load_8bit / load_4bit (bitsandbytes' numerics) stay unsupported."""
+    if decode_weight_format not in (None, "mxfp8"):
+        raise ValueError(f"decode_weight_format={decode_weight_format!r}: expected None or 'mxfp8'")
     if load_8bit or load_4bit:
         raise NotImplementedError("bitsandbytes quantised loading (BLD:51-62) is out of scope for the MI355X hot path")
     if model_base is not None:
@@ -146,6 +151,7 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bi
 
         warnings.warn(f"load_pretrained_model: no tokenizer could be loaded from {model_path!r} ({type(e).__name__}: {e}); returning tokenizer=None", RuntimeWarning)
         tokenizer = None
+    model.decode_weight_format = decode_weight_format
     model.finalize()
     context_len = cfg.extra.get("max_sequence_length", 2048)
     return tokenizer, model, image_processor, context_len

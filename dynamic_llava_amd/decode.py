@@ -127,9 +127,19 @@ class DecodeScheduler:
         torch.index_select(self.model.embed_tokens.weight, 0, st.cur_ids, out=st.h)
         h_cur, h_alt, delta = st.h, st.h2, None
         A = ops.GEMV_ADDNORM
+        # MXFP8 decoder weights (set_decode_weight_format): the four projections stream (q, scale) on dl_gemv_mx8; the two fused model-dtype launches
+        # (dl_gemv_qkv_attn, dl_gemv_gu_tp) are not used -- the unfused sequence runs instead (stand-alone attention, the predictor's decide)
+        mx8 = self.decode_weight_format == "mxfp8"
         for i, layer in enumerate(self.model.layers):
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
+            if mx8:
+                self._decode_layer_mx8(st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp)
+                if delta is not None:
+                    h_cur, h_alt = h_alt, h_cur
+                h_cur, h_alt = h_alt, h_cur
+                delta = st.dn
+                continue
             # q|k|v projection + single-split attention of a batch-1 layer in ONE launch (dl_gemv_qkv_attn: the attention workgroups fetch their
             # K/V rows while the weights stream and receive the projection as granules).  Same bodies as the two launches below, so the
             # results are bit-identical to them WHEN the stand-alone attention also runs four waves (KVSlabCache.eight_wave_single_split =
@@ -176,6 +186,32 @@ class DecodeScheduler:
         ops.gemv(self.lm_head.weight, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
         if use_tp and self.tp_side_stream:
             torch.cuda.current_stream().wait_stream(st.tp_stream)  # join before anything reads st.decision
+
+    def _decode_layer_mx8(self, st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp):
+        """One layer of _decode_step_gemv on MXFP8 weights: the unfused launch sequence of the model-dtype step with dl_gemv_mx8 in place of dl_gemv.
+        The residual stream ping-pongs exactly as there (the caller swaps h_cur / h_alt)."""
+        cfg, sc = self.config, self.config.sparse_config
+        nH, nKV, d, eps = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.rms_norm_eps
+        cos, sin = self._rope
+        A = ops.GEMV_ADDNORM
+        m = layer.mx8
+        ops.gemv_mx8(*m["qkv"], st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
+        if delta is not None:
+            h_cur, h_alt = h_alt, h_cur
+        if i == sc["sparse_layer"] and use_tp:  # F6: decision on the hidden state entering layer SL (DML:2377-2391)
+            if self.tp_side_stream:
+                st.tp_x.copy_(h_cur)
+                st.tp_stream.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(st.tp_stream):
+                    self.model.output_text_score_predictor.decide(st.tp_x, st.tp_ws, st.tp_logits, st.decision)
+            else:
+                self.model.output_text_score_predictor.decide(h_cur, st.tp_ws, st.tp_logits, st.decision)
+        L = cfg.num_hidden_layers
+        ops.attn_decode_rope(st.qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH),
+                             chunk_keys=cache.spec_chunk(ns), call_tag=(i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
+        ops.gemv_mx8(*m["o"], st.o, x=st.attn)
+        ops.gemv_mx8(*m["gu"], st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps)
+        ops.gemv_mx8(*m["down"], st.dn, x=st.gu)
 
     def _decode_step_gemm(self, st: _DecodeState, cache: KVSlabCache):
         """Decode step for batches past the GEMV range (round 5, `profiles/r05_decode_batch_paths.txt`).  Up to smallm_max_decode_batch (32) rows:
@@ -290,7 +326,7 @@ class DecodeScheduler:
         from .cache import _SINGLE_SPLIT_MAX_KEYS
         if self.single_split_keys_override is not None:  # tests: force the schedule to change inside a short generation
             return int(self.single_split_keys_override), int(self.single_split_keys_override)
-        if not (self.fuse_qkv_attn and st.B == 1 and st.use_gemv and st.qa_gran is not None):
+        if not (self.fuse_qkv_attn and st.B == 1 and st.use_gemv and st.qa_gran is not None) or self.decode_weight_format == "mxfp8":
             return _SINGLE_SPLIT_MAX_KEYS, _SINGLE_SPLIT_MAX_KEYS
         w = self.model.layers[0].w_qkv
         big = (w.numel() * w.element_size()) >= 130e6  # 13B-class stream
@@ -329,7 +365,7 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch)
+               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)

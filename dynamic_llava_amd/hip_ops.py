@@ -91,6 +91,9 @@ SIGNATURES = {
     "dl_text_predictor_workspace_bytes": (c_int64, [c_int, c_int]),
     "dl_gemv_max_batch": (c_int, [c_int, c_int]),
     "dl_gemv": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "dl_mx8_e_min": (c_int, [c_int]),
+    "dl_quantize_mx8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dl_gemv_mx8": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
     "dl_linear_splitk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dl_gemv_qkv_attn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "dl_gemv_gu_tp_workspace_bytes": (c_int64, [c_int]),
@@ -561,6 +564,49 @@ def gemv(w, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_
     _check(
         lib().dl_gemv(mode, _p(w), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(w.dtype), int(grid_cap), _stream()),
         "dl_gemv",
+    )
+    return y
+
+
+def quantize_mx8(w, model_dtype=None, err=None):
+    """MXFP8 codes of w [N, K] (K % 32 == 0) on the device: -> (q uint8 [N, K], scale uint8 [N, K/32]), bit-exact to mxfp8.quantize_mx8(w, model_dtype)
+    (model_dtype, default w.dtype, sets the smallest block exponent).  err: an int32 device tensor that is set to 1 when w holds a NaN / Inf; without it the
+    check is made here (one host sync)."""
+    _dev(w, err)
+    assert w.dim() == 2 and w.is_contiguous()
+    N, K = w.shape
+    if K % 32 != 0:
+        raise HipOpsError(f"quantize_mx8: K={K} is not a multiple of 32")
+    md = w.dtype if model_dtype is None else model_dtype
+    q = torch.empty((N, K), dtype=torch.uint8, device=w.device)
+    sc = torch.empty((N, K // 32), dtype=torch.uint8, device=w.device)
+    own = err is None
+    if own:
+        err = torch.zeros(1, dtype=torch.int32, device=w.device)
+    _check(lib().dl_quantize_mx8(_p(w), N, K, dtype_code(w.dtype), dtype_code(md), _p(q), _p(sc), _p(err), _stream()), "dl_quantize_mx8")
+    if own and int(err.item()) != 0:
+        raise ValueError("quantize_mx8: the weight holds NaN or Inf")
+    return q, sc
+
+
+def gemv_mx8(q, scale, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_w=None, eps=0.0, grid_cap=0):
+    """gemv() on MXFP8 weights: y[b,:] = W' @ prologue(x)[b,:], W' = q * 2^(scale - 127) per 32-element block (see include/dynllava.h).
+    q uint8 [N,K], scale uint8 [N,K/32]; y [B,N] (or [B,N/2] with GEMV_OUT_SILU_PAIR) in the activation dtype."""
+    _dev(q, scale, y, x, h_in, h_out, delta, norm_w)
+    assert q.dtype == torch.uint8 and scale.dtype == torch.uint8 and q.is_contiguous() and scale.is_contiguous() and y.stride(1) == 1
+    N, K = q.shape
+    assert scale.shape == (N, K // 32)
+    B = y.shape[0]
+    if (mode & 3) == GEMV_ADDNORM:
+        assert h_in.is_contiguous() and h_in.shape == (B, K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
+        xs = 0
+    else:
+        assert x.stride(1) == 1 and x.shape[0] == B
+        xs = x.stride(0)
+    _check(
+        lib().dl_gemv_mx8(mode, _p(q), _p(scale), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(y.dtype),
+                          int(grid_cap), _stream()),
+        "dl_gemv_mx8",
     )
     return y
 

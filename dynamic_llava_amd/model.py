@@ -115,6 +115,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self.single_split_keys_override = None  # tests only: see _single_split_max_keys
         self.min_keys_per_split = 64  # tests only: KVSlabCache.min_keys_per_split of the caches this model schedules
         self.debug_records = None  # dict filled by forward passes when set to {} (tests)
+        self.decode_weight_format = None  # "mxfp8": see set_decode_weight_format()
         self.eval()
 
     # ---- reference surface -----------------------------------------------------------------
@@ -170,6 +171,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         ops.require_gpu()
         if self.device.type != "cuda":
             raise ops.HipOpsError("the model must live on the GPU (no CPU path exists)")
+        if self.decode_weight_format == "mxfp8":
+            self._quantize_decoder_weights()  # W -> W' in place, BEFORE anything below copies the weights
         for l in self.model.layers:
             l.pack(operand_copies=self.packed_prefill_gemm, o_copy=self.tiles_o_proj)  # (weights replaced later: call finalize() again -- the operand-order copies are made here)
         self._lp_err = torch.zeros(1, dtype=torch.int32, device=self.device)
@@ -190,11 +193,51 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._fp_params = [w for l in self.model.layers for w in (l.self_attn.q_proj.weight, l.self_attn.k_proj.weight, l.self_attn.v_proj.weight, l.self_attn.o_proj.weight,
                                                                    l.mlp.gate_proj.weight, l.mlp.up_proj.weight, l.mlp.down_proj.weight)]
         self._fp = self._weights_fingerprint()
+        for l in self.model.layers:  # the decode step's MXFP8 codes of the fused weights (quantising W' reproduces W''s codes: nothing is written)
+            l.mx8 = None
+            if self.decode_weight_format == "mxfp8":
+                l.mx8 = {"qkv": ops.quantize_mx8(l.w_qkv), "o": ops.quantize_mx8(l.self_attn.o_proj.weight.data.contiguous()), "gu": ops.quantize_mx8(l.w_gu),
+                         "down": ops.quantize_mx8(l.mlp.down_proj.weight.data.contiguous())}
         self._packed = True
         self._build_rope(self.config.max_position_embeddings)
         self._dstate = None
         self._prefill_graphs = {}  # captured prefills hold the pointers of the tensors packed above
         return self
+
+    # ---- MXFP8 decoder weights -------------------------------------------------------------------
+    def set_decode_weight_format(self, fmt):
+        """Select the weight format the small-batch decode step streams.  None (default): the model dtype.  "mxfp8": OCP MXFP8 (mxfp8.py).
+
+        "mxfp8" quantises every decoder layer's q|k|v, o_proj, gate|up and down_proj weight and OVERWRITES the parameters in place with
+        W' = dequantize(quantize(W)), which is exact in the model dtype; finalize() then rebuilds every copy (operand-order copies, fingerprint, captured
+        graphs) from W', and the MXFP8 codes are kept beside the weights (layer.mx8).  The model is from then on exactly the model-dtype model with weights W':
+        prefill, CLIP, the projector, decode batches above gemv_max_decode_batch, use_cache=False and chunk-on-cache run their usual kernels on W'; decode
+        steps of <= gemv_max_decode_batch rows run the four projections on dl_gemv_mx8 (the lm_head, the predictors, embeddings and norms stay in the model
+        dtype).  Quantisation is idempotent (quantising W' again gives the same codes) but NOT reversible: set_decode_weight_format(None) restores the
+        model-dtype kernels, not W.  A decoder weight changed afterwards (load_state_dict, in-place edits) is re-quantised -- W'' = quantize(new W) overwrites
+        it -- by the next finalize(), which the weight-fingerprint check of generate() / forward() runs: FP8 codes of old weights are never served.
+        The lm_head, the CLIP tower and the KV cache are not quantised.  Extra memory: decode_weight_bytes()."""
+        if fmt not in (None, "mxfp8"):
+            raise ValueError(f"decode weight format {fmt!r}: expected None or 'mxfp8'")
+        self.decode_weight_format = fmt
+        self._packed = False
+        return self.finalize()  # (drops the decode state and its captured graphs: their keys and pointers belong to the old format)
+
+    def _quantize_decoder_weights(self):
+        from .mxfp8 import dequantize_mx8
+
+        for l in self.model.layers:
+            a, m = l.self_attn, l.mlp
+            for lin in (a.q_proj, a.k_proj, a.v_proj, a.o_proj, m.gate_proj, m.up_proj, m.down_proj):  # (blocks run along K inside a row: the fused weights give the same codes)
+                w = lin.weight.data
+                q, sc = ops.quantize_mx8(w.contiguous())
+                w.copy_(dequantize_mx8(q, sc, w.dtype))
+
+    def decode_weight_bytes(self) -> dict:
+        """Bytes the decode weight format keeps beside the parameters (MXFP8: codes + one scale byte per 32 weights of the four decoder projections)."""
+        nb = lambda t: t.numel() * t.element_size()
+        mx8 = sum(nb(q) + nb(sc) for l in self.model.layers for q, sc in (getattr(l, "mx8", None) or {}).values())
+        return {"format": self.decode_weight_format, "mxfp8": mx8, "total": mx8}
 
     def _build_rope(self, n_pos):
         """dynamic_modeling_llama.py:152-174,181-184: fp32 cos/sin of cat(freqs, freqs), rounded to the model dtype."""
@@ -289,6 +332,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "tiles_o_proj": self.tiles_o_proj, "tiles_o_proj_min_decode_batch": self.tiles_o_proj_min_decode_batch,
             "clip_tiles_gemm": getattr(self.get_vision_tower(), "tiles_gemm", None), "clip_tiles_max_batch": getattr(self.get_vision_tower(), "tiles_max_batch", None),
             "clip_tiles_ksplit": [getattr(self.get_vision_tower(), "tiles_ksplit_out", None), getattr(self.get_vision_tower(), "tiles_ksplit_fc2", None)],
+            "decode_weight_format": self.decode_weight_format,
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }

@@ -239,6 +239,22 @@ int dl_gemv(int mode, const void* W, int N, int K, const void* x, int64_t x_row_
             const void* delta, const void* norm_w, float eps, void* y, int64_t y_row_stride, int B, int dtype, int grid_cap,
             void* stream);
 
+/* ---- MXFP8 decoder weights (OCP Microscaling v1.0 MXFP8 along K; dynamic_llava_amd/mxfp8.py is the host reference) ----
+ * q: uint8 [N, K] row-major, OCP FP8 E4M3 "e4m3fn" codes (not the fnuz encoding); scale: uint8 [N, K/32] row-major, the E8M0 code e + 127 of
+ * the block of 32 consecutive K elements q[n, 32j .. 32j+31].  W' = q * 2^e.  No interleaving or swizzle.  K % 32 == 0.
+ * dl_mx8_e_min(dtype): the smallest block exponent the quantiser writes for a model of that dtype (-15 for fp16, -124 for bf16 / fp32): with it
+ * every W' is exactly representable in the model dtype, subnormals included.
+ * dl_quantize_mx8: per block, amax == 0 -> e = 0 and q = 0; else e = clamp(floor(log2(amax)) - 8, e_min(model_dtype), 127) and
+ * q = RNE(w / 2^e) to e4m3fn, saturated at +-448.  W: [N, K] of src_dtype.  A NaN / Inf weight sets *err_flag = 1 (may be NULL; never cleared
+ * here), the codes of its block are then undefined.
+ * dl_gemv_mx8: dl_gemv's contract with W replaced by (q, scale), modes DL_GEMV_PLAIN, DL_GEMV_ADDNORM and DL_GEMV_ADDNORM | DL_GEMV_OUT_SILU_PAIR,
+ * B <= dl_gemv_max_batch(K, dtype); dtype is that of x / h / y.  y = cast(fp32 sum of the products x * W'), one rounding; the ADDNORM prologue's
+ * h_out is bit-identical to dl_gemv's. */
+int dl_mx8_e_min(int dtype);
+int dl_quantize_mx8(const void* W, int64_t N, int K, int src_dtype, int model_dtype, void* q, void* scale, int32_t* err_flag, void* stream);
+int dl_gemv_mx8(int mode, const void* q, const void* scale, int N, int K, const void* x, int64_t x_row_stride, const void* h_in, void* h_out,
+                const void* delta, const void* norm_w, float eps, void* y, int64_t y_row_stride, int B, int dtype, int grid_cap, void* stream);
+
 /* ---- in-place packing of the kept rows of a just-appended chunk: replaces the per-row slice / cat / zero-pad of CU:165-241 for the
  * multi-round "new instruct" call (DML:2506-2521).  For n_layers consecutive layer slabs starting at k_slab0 / v_slab0 (layer_stride
  * elements apart; each [B, nKV, T_cap, d] with the given strides), the chunk of T tokens sits at slots [kv_len[b], kv_len[b] + T); rows
