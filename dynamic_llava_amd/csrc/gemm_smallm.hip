@@ -12,6 +12,7 @@
 //    v_mfma_f32_16x16x32: D[neuron][batch]; every lane ends up with 4 consecutive neurons of one batch row: stored directly, no
 //    cross-lane reduction.  Two accumulators per batch tile break the MFMA dependency chain.
 #include "dl_common.h"
+#include "splitk_reduce.h"
 
 namespace dl {
 
@@ -248,35 +249,6 @@ __global__ __launch_bounds__(NW * 64) void gemm_smallm_staged_kernel(const void*
   }
 }
 
-// Y[m,n] = cast(sum_s part[s,m,n]) in slice order.  N % 4 == 0.
-template <typename T>
-__global__ __launch_bounds__(256) void gemm_smallm_reduce_kernel(const float* __restrict__ part, int n_slices, int M, int N,
-                                                                  void* __restrict__ Y_, int64_t ldy) {
-  const int64_t nq = (int64_t)M * (N / 4);
-  for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < nq; idx += (int64_t)gridDim.x * 256) {
-    const int64_t m = idx / (N / 4);
-    const int n = (int)(idx - m * (N / 4)) * 4;
-    float4 s = *reinterpret_cast<const float4*>(part + m * N + n);
-    for (int k0 = 1; k0 < n_slices; k0 += 8) {  // the loads of up to eight slices are in flight together; the additions stay in slice order
-      float4 v[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = *reinterpret_cast<const float4*>(part + ((int64_t)(k0 + j < n_slices ? k0 + j : k0) * M + m) * N + n);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (k0 + j < n_slices) {
-          s.x += v[j].x;
-          s.y += v[j].y;
-          s.z += v[j].z;
-          s.w += v[j].w;
-        }
-    }
-    store1<T>(Y_, m * ldy + n, s.x);
-    store1<T>(Y_, m * ldy + n + 1, s.y);
-    store1<T>(Y_, m * ldy + n + 2, s.z);
-    store1<T>(Y_, m * ldy + n + 3, s.w);
-  }
-}
-
 // slices: enough to (a) fit the X slice in LDS and (b) give the 256 CUs ~8 waves each.
 static int sm_slices(int M, int N, int K, int want, int variant) {
   const int units = K / kSmKUnit;
@@ -320,16 +292,6 @@ static int sm_go(const void* X, int64_t ldx, const void* W, void* Y, int64_t ldy
   if (gx > cap) gx = cap;
   hipLaunchKernelGGL(kfn, dim3((unsigned)gx, (unsigned)n_slices), dim3(NW * 64), smem, st, X, ldx, W, Y, ldy, part, M, N, K, n_slices, direct);
   return DL_OK;
-}
-
-template <typename T>
-static void sm_reduce(float* part, void* Y, int64_t ldy, int M, int N, int n_slices, hipStream_t st) {
-  if (n_slices > 1) {
-    const int64_t nq = (int64_t)M * (N / 4);
-    const int64_t blocks = (nq + 255) / 256;
-    hipLaunchKernelGGL((gemm_smallm_reduce_kernel<T>), dim3((unsigned)(blocks < 1024 ? blocks : 1024)), dim3(256), 0, st, part, n_slices, M, N, Y,
-                       ldy);
-  }
 }
 
 template <typename T, int NB, int KC, int NW>

@@ -54,11 +54,18 @@ class _DecodeState:
             ops.gemm_smallm_ok(B, n, k, dtype) for n, k in (((nH + 2 * nKV) * d, H), (H, nH * d), (2 * I, H), (H, I), (V, H))
         )
         self.lin_ws = torch.empty(8 * B * max(2 * I, V), dtype=torch.float32, device=device) if self.use_smallm else None
+        # MXFP8 decoder weights with set_decode_weight_format(max_batch=): the four projections of such a batch stream the codes (dl_gemm_mx8) -- row-major x, no
+        # operand-order copies on this route; the lm_head keeps the route chosen above
+        mx_shapes = (((nH + 2 * nKV) * d, H), (H, nH * d), (2 * I, H), (H, I))
+        mb = getattr(model, "mx8_max_decode_batch", None)
+        self.use_mx8_gemm = ((not self.use_gemv) and model.decode_weight_format == "mxfp8" and mb is not None and B <= mb
+                             and getattr(model.model.layers[0], "mx8", None) is not None and all(ops.gemm_mx8_ok(B, n, k, dtype) for n, k in mx_shapes))
+        self.mx8_ws = torch.empty(max(int(ops.lib().dl_gemm_mx8_workspace_bytes(B, n, k, 0)) for n, k in mx_shapes) // 4, dtype=torch.float32, device=device) if self.use_mx8_gemm else None
         # round 5: decode batches of packed_decode_mlp_min_batch..32 rows (configs[2] / [3]: 32) run their MLP on dl_linear_packed -- gate|up with the SiLU * up
         # epilogue writing `act` in fragment order, down_proj leaving 4 k ranges of fp32 partial sums for the residual-add / RMSNorm launch
         # (tools/bench_linear_packed.py, M = 32: 38.4 vs 44.8 us and 25.5 vs 31.7 us against the library) -- whatever q|k|v and o_proj run on
         l0 = model.model.layers[0]
-        self.use_lp_mlp = (not self.use_gemv and model.packed_decode_mlp_min_batch <= B <= 32 and model.packed_decode_mlp and getattr(l0, "wp_gu", None) is not None
+        self.use_lp_mlp = (not self.use_gemv and not self.use_mx8_gemm and model.packed_decode_mlp_min_batch <= B <= 32 and model.packed_decode_mlp and getattr(l0, "wp_gu", None) is not None
                            and getattr(l0, "wp_down", None) is not None)
         if self.use_lp_mlp:
             n_el = lambda cols: int(ops.lib().dl_packed_x_bytes(B, cols)) // 2
@@ -66,7 +73,7 @@ class _DecodeState:
             self.act_pk = torch.empty(n_el(I), dtype=dtype, device=device)
             self.lp_parts = torch.empty(4 * B * H, dtype=torch.float32, device=device)
             self.qkv_parts = torch.empty(2 * B * (nH + 2 * nKV) * d, dtype=torch.float32, device=device)  # q|k|v's two k ranges, added by the attention launch
-        self.o_parts = torch.empty(8 * B * H, dtype=torch.float32, device=device) if (self.use_smallm and B <= 32 and getattr(l0, "wp_o", None) is not None) else None  # o_proj's k-range slices (dl_linear_tiles)
+        self.o_parts = torch.empty(8 * B * H, dtype=torch.float32, device=device) if (self.use_smallm and not self.use_mx8_gemm and B <= 32 and getattr(l0, "wp_o", None) is not None) else None  # o_proj's k-range slices (dl_linear_tiles)
         self.graphs = {}  # captured decode steps, keyed by (slab, split factors, ...): see _run_decode_steps
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
@@ -218,7 +225,8 @@ class DecodeScheduler:
         o_proj -- and q|k|v below packed_decode_qkv_min_batch (16) rows -- on dl_gemm_smallm (row-major weights streamed into the matrix cores, fp32
         split-K partials added by the residual-add / RMSNorm launch); from packed_decode_mlp_min_batch (4) rows the MLP, from 16 rows q|k|v too, on
         dl_linear_packed (operand-order weight copies; SiLU * up in the epilogue, down_proj as 4 k ranges of partial sums; the norm launches write the
-        GEMMs' input in fragment order): 7 launches per layer.  Larger batches, or a model without operand copies: library GEMMs."""
+        GEMMs' input in fragment order): 7 launches per layer.  Larger batches, or a model without operand copies: library GEMMs.
+        MXFP8 decoder weights with max_batch >= B (st.use_mx8_gemm): the four projections of every layer on dl_gemm_mx8 instead (_decode_layer_gemm_mx8)."""
         cfg, sc = self.config, self.config.sparse_config
         nH, nKV, d = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         eps, L, SL = cfg.rms_norm_eps, cfg.num_hidden_layers, sc["sparse_layer"]
@@ -238,6 +246,9 @@ class DecodeScheduler:
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
             tag = (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1
+            if st.use_mx8_gemm:
+                self._decode_layer_gemm_mx8(st, cache, i, layer, lens, ns, tag)
+                continue
             if lp_qkv and qkv_parts and cache.keys_in_flight(ns, st.B * nH) == 64:
                 # round 6 (verdict r5 item 2c): the projection's two k ranges stay fp32 partial sums and the RoPE / append / attention launch adds them (each (row, head)
                 # workgroup the 3 x head_dim values it reads): no hand-over inside the projection's launch.  In the step (profiles/r06_decode_qkv_parts.txt): the
@@ -291,6 +302,25 @@ class DecodeScheduler:
             ops.gemm_smallm(st.x, self.lm_head.weight, out=st.logits, workspace=ws)
         else:
             torch.matmul(st.x, self.lm_head.weight.t(), out=st.logits)
+
+    def _decode_layer_gemm_mx8(self, st, cache, i, layer, lens, ns, tag):
+        """One layer of _decode_step_gemm on MXFP8 weights (set_decode_weight_format(max_batch=)): its dl_gemm_smallm sequence with dl_gemm_mx8 streaming layer.mx8 --
+        q|k|v in the model dtype for the RoPE / append / attention launch, o_proj, gate|up and down_proj as fp32 split-K partial sums that the residual-add / RMSNorm and
+        SiLU * up launches add.  7 launches per layer (8 when q|k|v is split over K), x row-major throughout."""
+        cfg = self.config
+        nH, nKV, d, eps, L = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.rms_norm_eps, cfg.num_hidden_layers
+        cos, sin = self._rope
+        m, ws = layer.mx8, st.mx8_ws
+        ops.gemm_mx8(st.x, *m["qkv"], out=st.qkv, workspace=ws)
+        ops.attn_decode_rope(st.qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH),
+                             chunk_keys=cache.spec_chunk(ns), call_tag=tag)
+        parts, _ = ops.gemm_mx8_parts(st.attn, *m["o"], ws)
+        ops.add_rmsnorm_parts(st.h, parts, layer.post_attention_layernorm.weight, eps, out=st.x)
+        parts, _ = ops.gemm_mx8_parts(st.x, *m["gu"], ws)
+        ops.silu_mul_parts(parts, st.act)
+        parts, _ = ops.gemm_mx8_parts(st.act, *m["down"], ws)
+        nw = self.model.norm.weight if i + 1 == L else self.model.layers[i + 1].input_layernorm.weight
+        ops.add_rmsnorm_parts(st.h, parts, nw, eps, out=st.x)
 
     def _pooled_cache(self, B, t_need):
         """generate() owns its cache, so the slab is reused across calls: stable pointers keep the captured hipGraphs valid."""
@@ -365,7 +395,7 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format)
+               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)

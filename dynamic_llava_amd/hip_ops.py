@@ -94,6 +94,9 @@ SIGNATURES = {
     "dl_mx8_e_min": (c_int, [c_int]),
     "dl_quantize_mx8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_gemv_mx8": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "dl_gemm_mx8_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "dl_gemm_mx8_slices": (c_int, [c_int, c_int, c_int, c_int]),
+    "dl_gemm_mx8": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dl_linear_splitk": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "dl_gemv_qkv_attn_workspace_bytes": (c_int64, [c_int, c_int, c_int]),
     "dl_gemv_gu_tp_workspace_bytes": (c_int64, [c_int]),
@@ -609,6 +612,53 @@ def gemv_mx8(q, scale, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=
         "dl_gemv_mx8",
     )
     return y
+
+
+MX8_PLAIN, MX8_PARTS = 0, 1  # dl_gemm_mx8's epilogues (include/dynllava.h)
+
+
+def gemm_mx8_ok(M, N, K, dtype):
+    """Shapes dl_gemm_mx8 takes (gemm_smallm_ok's: the decode step keeps its model-dtype route otherwise)."""
+    return dtype in (torch.bfloat16, torch.float16) and 0 < M <= 32 and K % 256 == 0 and N % 4 == 0
+
+
+def _gemm_mx8_call(x, q, scale, out, workspace, n_slices, epilogue):
+    assert x.dim() == 2 and x.stride(1) == 1 and q.dim() == 2 and q.dtype == torch.uint8 and scale.dtype == torch.uint8 and q.is_contiguous() and scale.is_contiguous()
+    M, K = x.shape
+    N = q.shape[0]
+    assert q.shape[1] == K and scale.shape == (N, K // 32)
+    assert workspace is None or (workspace.dtype == torch.float32 and workspace.is_contiguous())
+    _check(
+        lib().dl_gemm_mx8(_p(x), x.stride(0), _p(q), _p(scale), _p(out), 0 if out is None else out.stride(0), _p(workspace), 0 if workspace is None else workspace.numel() * 4,
+                          M, N, K, int(n_slices), int(epilogue), dtype_code(x.dtype), _stream()),
+        "dl_gemm_mx8",
+    )
+
+
+def gemm_mx8(x, q, scale, out=None, workspace=None, n_slices=0):
+    """out[M,N] = x[M,K] @ W'^T for 1 <= M <= 32 rows on MXFP8 weights (q uint8 [N,K], scale uint8 [N,K/32]: quantize_mx8's output; W' = q * 2^(scale - 127)).
+    x, out: bf16 / fp16.  workspace: fp32 scratch for the split-K partials (allocated here if None -- pass a persistent one under hipGraph capture; one that
+    is too small is an error)."""
+    _dev(x, q, scale, out, workspace)
+    M, N = x.shape[0], q.shape[0]
+    if out is None:
+        out = torch.empty((M, N), dtype=x.dtype, device=x.device)
+    assert out.shape == (M, N) and out.stride(1) == 1 and out.dtype == x.dtype
+    if workspace is None:
+        need = int(lib().dl_gemm_mx8_workspace_bytes(M, N, x.shape[1], int(n_slices)))
+        workspace = torch.empty(max(need // 4, 4), dtype=torch.float32, device=x.device)
+    _gemm_mx8_call(x, q, scale, out, workspace, n_slices, MX8_PLAIN)
+    return out
+
+
+def gemm_mx8_parts(x, q, scale, workspace, n_slices=0):
+    """x @ W'^T left as fp32 split-K partials in `workspace` (viewed [slices, M, N]); returns (parts, slices) for add_rmsnorm_parts / silu_mul_parts, which add
+    the slices themselves (no reduce launch) -- gemm_smallm_parts on MXFP8 weights."""
+    _dev(x, q, scale, workspace)
+    M, N = x.shape[0], q.shape[0]
+    _gemm_mx8_call(x, q, scale, None, workspace, n_slices, MX8_PARTS)
+    s = int(lib().dl_gemm_mx8_slices(M, N, x.shape[1], int(n_slices)))
+    return workspace[: s * M * N].view(s, M, N), s
 
 
 def gemv_qkv_attn_workspace(n_heads, n_kv_heads, head_dim, device):

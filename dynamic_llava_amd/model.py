@@ -116,6 +116,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self.min_keys_per_split = 64  # tests only: KVSlabCache.min_keys_per_split of the caches this model schedules
         self.debug_records = None  # dict filled by forward passes when set to {} (tests)
         self.decode_weight_format = None  # "mxfp8": see set_decode_weight_format()
+        # MXFP8 only: decode steps of gemv_max_decode_batch < B <= this many rows stream the codes too (dl_gemm_mx8); None: the codes are used in the GEMV range only
+        self.mx8_max_decode_batch = None
         self.eval()
 
     # ---- reference surface -----------------------------------------------------------------
@@ -205,7 +207,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         return self
 
     # ---- MXFP8 decoder weights -------------------------------------------------------------------
-    def set_decode_weight_format(self, fmt):
+    def set_decode_weight_format(self, fmt, max_batch=None):
         """Select the weight format the small-batch decode step streams.  None (default): the model dtype.  "mxfp8": OCP MXFP8 (mxfp8.py).
 
         "mxfp8" quantises every decoder layer's q|k|v, o_proj, gate|up and down_proj weight and OVERWRITES the parameters in place with
@@ -216,10 +218,17 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         dtype).  Quantisation is idempotent (quantising W' again gives the same codes) but NOT reversible: set_decode_weight_format(None) restores the
         model-dtype kernels, not W.  A decoder weight changed afterwards (load_state_dict, in-place edits) is re-quantised -- W'' = quantize(new W) overwrites
         it -- by the next finalize(), which the weight-fingerprint check of generate() / forward() runs: FP8 codes of old weights are never served.
-        The lm_head, the CLIP tower and the KV cache are not quantised.  Extra memory: decode_weight_bytes()."""
-        if fmt not in (None, "mxfp8"):
-            raise ValueError(f"decode weight format {fmt!r}: expected None or 'mxfp8'")
+        The lm_head, the CLIP tower and the KV cache are not quantised.  Extra memory: decode_weight_bytes().
+
+        max_batch (None, or gemv_max_decode_batch .. 32; "mxfp8" only): decode steps of gemv_max_decode_batch < B <= max_batch rows ALSO stream the codes -- the
+        four projections run on dl_gemm_mx8 (q|k|v into dl_attn_decode_rope, o_proj / down_proj as fp32 partial sums into dl_add_rmsnorm_parts, gate|up into
+        dl_silu_mul_parts) when the kernel takes all four shapes (16-bit model dtype, K % 256 == 0, N % 4 == 0; otherwise the step silently keeps its model-dtype
+        kernels).  None (default): such steps run the model-dtype kernels on W'.  Larger batches, prefill, use_cache=False and chunk-on-cache are unaffected."""
+        from .mxfp8 import check_decode_weight_format
+
+        check_decode_weight_format(fmt, max_batch, self.gemv_max_decode_batch)
         self.decode_weight_format = fmt
+        self.mx8_max_decode_batch = None if max_batch is None else int(max_batch)
         self._packed = False
         return self.finalize()  # (drops the decode state and its captured graphs: their keys and pointers belong to the old format)
 
@@ -234,7 +243,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 w.copy_(dequantize_mx8(q, sc, w.dtype))
 
     def decode_weight_bytes(self) -> dict:
-        """Bytes the decode weight format keeps beside the parameters (MXFP8: codes + one scale byte per 32 weights of the four decoder projections)."""
+        """Bytes the decode weight format keeps beside the parameters (MXFP8: codes + one scale byte per 32 weights of the four decoder projections).
+        The same with and without set_decode_weight_format's max_batch: dl_gemm_mx8 reads the one row-major copy of the codes.  The operand-order weight copies
+        of the model-dtype GEMMs (+11.9 GB at 7B) are still made in this mode -- the prefill runs on them -- and are not counted here."""
         nb = lambda t: t.numel() * t.element_size()
         mx8 = sum(nb(q) + nb(sc) for l in self.model.layers for q, sc in (getattr(l, "mx8", None) or {}).values())
         return {"format": self.decode_weight_format, "mxfp8": mx8, "total": mx8}
@@ -332,7 +343,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "tiles_o_proj": self.tiles_o_proj, "tiles_o_proj_min_decode_batch": self.tiles_o_proj_min_decode_batch,
             "clip_tiles_gemm": getattr(self.get_vision_tower(), "tiles_gemm", None), "clip_tiles_max_batch": getattr(self.get_vision_tower(), "tiles_max_batch", None),
             "clip_tiles_ksplit": [getattr(self.get_vision_tower(), "tiles_ksplit_out", None), getattr(self.get_vision_tower(), "tiles_ksplit_fc2", None)],
-            "decode_weight_format": self.decode_weight_format,
+            "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch,
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }

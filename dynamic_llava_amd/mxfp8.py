@@ -106,3 +106,52 @@ def dequantize_mx8(q: torch.Tensor, scale: torch.Tensor, dtype: torch.dtype = to
 def mx8_bytes(N: int, K: int) -> int:
     """Bytes of one [N, K] MXFP8 weight (codes + scales)."""
     return N * K + N * (K // BLOCK)
+
+
+# ---- decode batches of 4..32 rows: what the host computes for dl_gemm_mx8 (csrc/gemm_mx8.hip) ----
+GEMM_MAX_M = 32          # rows dl_gemm_mx8 takes
+GEMM_K_UNIT = 256        # K slices are multiples of the kernel's chunk
+_GEMM_WAVES = 8
+_GEMM_STAGE_BYTES = 16 * (GEMM_K_UNIT + 16) + 16 * 8  # per wave: 16 code rows of 256 + 16 bytes, 16 x 8 scale bytes
+_GEMM_LDS_BYTES = 150 * 1024
+
+
+def check_decode_weight_format(fmt, max_batch, gemv_max_decode_batch: int) -> None:
+    """Argument rule of set_decode_weight_format / load_pretrained_model: fmt is None or "mxfp8"; max_batch is None or an int in [gemv_max_decode_batch, 32] and needs
+    fmt == "mxfp8".  Raises ValueError."""
+    if fmt not in (None, "mxfp8"):
+        raise ValueError(f"decode weight format {fmt!r}: expected None or 'mxfp8'")
+    if max_batch is None:
+        return
+    if fmt is None:
+        raise ValueError("max_batch needs the decode weight format 'mxfp8'")
+    if isinstance(max_batch, bool) or not isinstance(max_batch, int) or not (gemv_max_decode_batch <= max_batch <= GEMM_MAX_M):
+        raise ValueError(f"max_batch={max_batch!r}: expected None or an int in [{gemv_max_decode_batch}, {GEMM_MAX_M}]")
+
+
+def gemm_mx8_slices(M: int, N: int, K: int, n_slices: int = 0) -> int:
+    """The split-K factor dl_gemm_mx8 uses for a call (dl_gemm_mx8_slices); 0 for a shape it rejects.  n_slices 0 = automatic: 4 for the wide projections (at least
+    1024 sixteen-neuron tiles), 8 otherwise; raised until one K slice of X (16 or 32 rows of the 16-bit dtype, rows padded by 8 elements) fits the LDS left beside the
+    eight waves' staging; never more than K / 256."""
+    if not (0 < M <= GEMM_MAX_M and N > 0 and K > 0 and K % GEMM_K_UNIT == 0 and N % 4 == 0 and 0 <= n_slices <= 64):
+        return 0
+    units = K // GEMM_K_UNIT
+    rows = 16 if M <= 16 else 32
+    budget = _GEMM_LDS_BYTES - _GEMM_WAVES * _GEMM_STAGE_BYTES
+    max_ks = (budget // (rows * 2) - 8) // GEMM_K_UNIT * GEMM_K_UNIT
+    s_lds = 1
+    while -(-units // s_lds) * GEMM_K_UNIT > max_ks:
+        s_lds += 1
+    s = n_slices if n_slices > 0 else (4 if (N + 15) // 16 >= 1024 else 8)
+    return min(max(s, s_lds), units)
+
+
+def gemm_mx8_slice_bounds(K: int, slices: int):
+    """[(k0, k1)] of every slice: K / 256 units dealt out as evenly as integer division allows (slice s covers units [units*s // slices, units*(s+1) // slices))."""
+    units = K // GEMM_K_UNIT
+    return [(units * s // slices * GEMM_K_UNIT, units * (s + 1) // slices * GEMM_K_UNIT) for s in range(slices)]
+
+
+def gemm_mx8_workspace_bytes(M: int, N: int, K: int, n_slices: int = 0) -> int:
+    """Bytes of the fp32 workspace of a dl_gemm_mx8 call (dl_gemm_mx8_workspace_bytes): slices x M x N partial sums."""
+    return gemm_mx8_slices(M, N, K, n_slices) * M * N * 4

@@ -255,6 +255,23 @@ int dl_quantize_mx8(const void* W, int64_t N, int K, int src_dtype, int model_dt
 int dl_gemv_mx8(int mode, const void* q, const void* scale, int N, int K, const void* x, int64_t x_row_stride, const void* h_in, void* h_out,
                 const void* delta, const void* norm_w, float eps, void* y, int64_t y_row_stride, int B, int dtype, int grid_cap, void* stream);
 
+/* ---- decode GEMM on MXFP8 weights for 4..32 rows: Y[M,N] = X[M,K] @ W'[N,K]^T with W' = (q, scale) as above (the nn.Linear calls of DML:1011-1013,
+ * 1127 and 328 when a batch of rows is decoded on MXFP8 decoder weights).  dl_gemm_smallm's structure (X resident in LDS, a wave streams 16 neurons
+ * through wave-private LDS into v_mfma_f32_16x16x32, split-K over n_slices) on one byte per weight.  1 <= M <= 32, bf16 / f16 X and Y, K % 256 == 0,
+ * N % 4 == 0, ldx % 8 == 0; ldx / ldy: row strides (elements).  Numerics: dl_gemv_mx8's -- exact products with W', fp32 accumulation (the codes are
+ * converted at unit scale, every K = 32 MFMA covers one scale block and 2^e is applied to its fp32 result), one rounding to the output dtype.
+ * n_slices: split-K factor (0 = auto; raised when the X slice would not fit LDS); dl_gemm_mx8_slices: the effective factor.
+ * epilogue DL_MX8_PLAIN: Y in the dtype (one slice: written by the kernel; more: the fp32 partials go to `workspace` and a second launch adds them in
+ * slice order).  DL_MX8_PARTS: the fp32 partials [slices][M][N] are left in `workspace` (always, even for one slice; Y may be NULL) for
+ * dl_add_rmsnorm_parts / dl_silu_mul_parts -- dl_gemm_smallm's defer_reduce layout.  workspace: 16-byte aligned, workspace_bytes >=
+ * dl_gemm_mx8_workspace_bytes(M, N, K, n_slices) whenever partials are written (checked: DL_ERR_ARG, nothing is launched). */
+#define DL_MX8_PLAIN 0
+#define DL_MX8_PARTS 1
+int64_t dl_gemm_mx8_workspace_bytes(int M, int N, int K, int n_slices);
+int dl_gemm_mx8_slices(int M, int N, int K, int n_slices);
+int dl_gemm_mx8(const void* X, int64_t ldx, const void* q, const void* scale, void* Y, int64_t ldy, void* workspace, int64_t workspace_bytes, int M,
+                int N, int K, int n_slices, int epilogue, int dtype, void* stream);
+
 /* ---- in-place packing of the kept rows of a just-appended chunk: replaces the per-row slice / cat / zero-pad of CU:165-241 for the
  * multi-round "new instruct" call (DML:2506-2521).  For n_layers consecutive layer slabs starting at k_slab0 / v_slab0 (layer_stride
  * elements apart; each [B, nKV, T_cap, d] with the given strides), the chunk of T tokens sits at slots [kv_len[b], kv_len[b] + T); rows
