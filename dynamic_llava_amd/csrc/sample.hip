@@ -1,0 +1,376 @@
+// Device-side sampling: temperature, top-k, top-p and the draw of one decode step, with dl_decode_advance's bookkeeping.
+// The rule is dynamic_llava_amd/sampling.py (the contract this kernel is tested against); in short, per row:
+//   z = logit / T (IEEE division); banned ids (EOS while step < min_new_tokens) are out;
+//   top-k keeps z >= (k-th largest z), ties included; w = expf(z - zmax), m = floor(w * 2^40) as a 64-bit integer;
+//   top-p keeps v iff S(z_v) > floor((1 - top_p) * M), S(x) = mass of the survivors with z <= x, M = their total mass;
+//   Philox4x32-10(counter = (step, row_base + row, 0, 0), key = seed) -> r64; t = umul64hi(r64, K), K = kept mass;
+//   token = lowest index whose inclusive prefix sum of kept masses (index order) exceeds t.
+//
+// One workgroup of 1024 threads per row.  Thread t owns the NE consecutive vocabulary entries starting at t * NE.  A 16-bit row is kept in registers
+// after one round of 16-byte loads (NE = 32 raw logits + their 32 weights for up to 32768 entries; 64 raw logits, weights recomputed, up to 65536);
+// an fp32 row (the model's step buffer is 16-bit: fp32 is the small-model / test route) is read again from L2 in every pass instead.
+// z is monotone in the logit, so both thresholds are KEY values: an order-preserving integer key per entry (the raw 16 bits of a bf16 / fp16 logit --
+// distinct 16-bit logits give distinct z; the 32 bits of z itself for fp32 logits, where neighbouring logits can round to one z when T > 1), and one
+// radix descent over the key's bytes finds "the smallest key whose inclusive ascending cumulative weight exceeds thr": weight 1 and thr = N - k for
+// top-k, weight m and thr = floor((1 - p) M) for top-p.
+// Each level is one LDS histogram of 64-bit integers filled with integer atomics (order-independent: the result is the same in every run), 16 copies
+// per bin indexed by lane so that the few bins a narrow logit distribution hits are not one serialised address.  The draw is one 64-bit block scan of
+// the per-thread kept masses (index order = thread order) and a walk over one thread's registers.  Every loop has a fixed trip count; no workspace.
+#include "dl_common.h"
+
+namespace dl {
+
+constexpr int kSampleMassBits = 40;  // sampling.py S_BITS
+constexpr int kSampleMaxV = 65536;   // V * 2^40 < 2^63
+constexpr int kHistCopies = 16;
+
+// floor(w * 2^40) for 0 <= w <= 1 (exact: a shift of the significand)
+__device__ __forceinline__ uint64_t sample_mass(float w) {
+  const uint32_t u = __float_as_uint(w);
+  const int e = (int)((u >> 23) & 255u);
+  if (e == 0 || e > 127 || (u >> 31)) return 0;  // zero / denormal (< 2^-126) / negative / not a weight (> 1, inf, NaN)
+  const uint64_t mant = (uint64_t)((u & 0x7fffffu) | 0x800000u);
+  const int sh = e - 127 - 23 + kSampleMassBits;
+  return sh >= 0 ? (mant << sh) : (sh > -24 ? (mant >> (-sh)) : 0ull);
+}
+
+// order-preserving keys; key 0 is reserved for entries that take no part (banned, past the end of the row)
+__device__ __forceinline__ uint32_t sample_key16(uint32_t u) {
+  u &= 0xffffu;
+  if (u == 0x8000u) u = 0;  // -0.0 == +0.0
+  return (u & 0x8000u) ? (~u & 0xffffu) : (u | 0x8000u);
+}
+__device__ __forceinline__ uint32_t sample_key32(float f) {
+  uint32_t u = __float_as_uint(f);
+  if (u == 0x80000000u) u = 0;
+  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1, uint32_t (&out)[4]) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
+    c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
+    k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+  }
+  out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// inclusive scan over the 64 lanes of a wave
+__device__ __forceinline__ uint64_t wave_scan_u64(uint64_t v, int lane) {
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const uint64_t t = (uint64_t)__shfl_up((unsigned long long)v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+struct dl_sample_params_dev {  // == dl_sample_params (include/dynllava.h)
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint32_t seed_lo, seed_hi;
+  int32_t row_base;
+  int32_t reserved[2];
+};
+
+template <typename T, int R>
+__global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restrict__ logits, int64_t row_stride, int V, int64_t* __restrict__ next_ids,
+                                                              int64_t* __restrict__ out_ids, int out_cap, int32_t* __restrict__ step,
+                                                              int32_t* __restrict__ finished, int eos_id, int eos_id2, int eos_id3, int pad_id,
+                                                              int32_t* __restrict__ kv_len_full, int32_t* __restrict__ kv_len_sparse,
+                                                              const int32_t* __restrict__ decision, int min_new_tokens,
+                                                              const dl_sample_params_dev* __restrict__ prm, uint8_t* __restrict__ kept_mask) {
+  constexpr int VE = Elem<T>::kVec, NE = R * VE;
+  constexpr bool kStream = R == 0;       // fp32 logits: nothing is held, every pass reads the thread's entries again (the row stays in L2)
+  constexpr bool k16 = VE == 8;          // 16-bit logits: keys are the raw bits
+  constexpr bool kStoreW = !kStream && NE <= 32;  // weights kept in registers (else recomputed where they are needed: same value every time)
+  constexpr int KB = k16 ? 2 : 4;        // key bytes = radix levels
+  constexpr int NRAW = kStream ? 1 : NE / 2, NW = kStoreW ? NE : 1, NVALID = kStream ? 1 : (NE + 31) / 32;
+  static_assert(kStream != k16, "register-resident rows for 16-bit logits, streamed rows for fp32");
+  const int ne = kStream ? (V + 1023) / 1024 : NE;  // entries per thread: thread t owns [t * ne, (t + 1) * ne)
+  using S = typename Elem<T>::storage;
+  __shared__ unsigned long long hist[256 * kHistCopies];
+  __shared__ unsigned long long red[256];
+  __shared__ unsigned long long s_wave[16];
+  __shared__ float s_fmax[16];
+  __shared__ unsigned long long s_thr;
+  __shared__ int s_bin, s_tok;
+  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  int st_fin = 0, st_step = 0, st_dec = 1, st_full = 0, st_sparse = 0;
+  if (tid == 0) {
+    if (finished) st_fin = finished[b];
+    if (step) st_step = step[b];
+    if (decision) st_dec = decision[b];
+    if (kv_len_full) st_full = kv_len_full[b];
+    if (kv_len_sparse) st_sparse = kv_len_sparse[b];
+    s_tok = 0;
+  }
+  const int cur_step = step ? step[b] : 0;        // uniform over the workgroup
+  const int row_done = finished ? finished[b] : 0;  // a finished row emits pad_id whatever its logits say: nothing to select
+  if (!row_done) {
+    const bool ban = eos_id >= 0 && min_new_tokens > 0 && cur_step < min_new_tokens;
+    const int banned = ban ? eos_id : -1, banned2 = ban ? eos_id2 : -1, banned3 = ban ? eos_id3 : -1;
+    const float temp = prm->temperature;  // finite and > 0: validated by the host (sampling.normalize_params) before the block is written
+    const int top_k = prm->top_k;
+    const float top_p = prm->top_p;
+
+    // `fresh` hides a register's value from the optimiser (see below)
+    auto fresh = [](uint32_t x) -> uint32_t {
+      asm volatile("" : "+v"(x));
+      return x;
+    };
+    // ---- the row: NE consecutive entries per thread ----
+    const S* row = reinterpret_cast<const S*>(logits) + (int64_t)b * row_stride;
+    const bool vec_ok = (row_stride % VE == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
+    uint32_t raw[NRAW];
+    float w[NW];
+    uint32_t valid[NVALID] = {};  // bit j: entry j takes part (inside the row, not banned)
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
+      const int v0 = (int)fresh((uint32_t)((tid * R + r) * VE));
+      uint4 q = make_uint4(0u, 0u, 0u, 0u);
+      if (vec_ok && v0 + VE <= V) {
+        q = *reinterpret_cast<const uint4*>(row + v0);
+      } else {
+        uint32_t t4[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int e = 0; e < VE; ++e) {
+          if (v0 + e < V) {
+            t4[e >> 1] |= (uint32_t)row[v0 + e] << (16 * (e & 1));
+          }
+        }
+        q = make_uint4(t4[0], t4[1], t4[2], t4[3]);
+      }
+      const uint32_t q4[4] = {q.x, q.y, q.z, q.w};
+#pragma unroll
+      for (int e = 0; e < VE; ++e) {
+        const int v = v0 + e;
+        if (v < V && v != banned && v != banned2 && v != banned3) valid[(r * VE + e) >> 5] |= 1u << ((r * VE + e) & 31);
+      }
+#pragma unroll
+      for (int i = 0; i < 4; ++i) raw[r * 4 + i] = q4[i];
+    }
+    // Keys and masses are a few instructions each and are recomputed at every use: `fresh` hides a register's value from the optimiser, which would
+    // otherwise keep all NE keys and all NE 64-bit masses alive across the passes below (3 * NE registers: more than a 1024-thread workgroup has).
+    auto is_valid = [&](int j) -> bool {
+      if constexpr (kStream) {
+        const int v = tid * ne + j;
+        return v < V && v != banned && v != banned2 && v != banned3;
+      } else {
+        return (fresh(valid[j >> 5]) >> (j & 31)) & 1u;
+      }
+    };
+    auto z_of = [&](int j) -> float {
+      if constexpr (kStream) {
+        const int v = tid * ne + j;
+        return (v < V ? load1<T>(row, v) : 0.f) / temp;
+      } else {
+        return Elem<T>::to_f((S)((fresh(raw[j >> 1]) >> (16 * (j & 1))) & 0xffffu)) / temp;
+      }
+    };
+    // (a logit of -inf takes no part either -- the rule's `z > -inf`: keys up to -inf's own become 0)
+    auto key_of = [&](int j) -> uint32_t {
+      if (!is_valid(j)) return 0u;
+      if constexpr (!k16) {
+        const uint32_t key = sample_key32(z_of(j));  // the rule is stated on z: fp32 logits next to each other can share one z when T > 1
+        return key > 0x007fffffu ? key : 0u;
+      } else {
+        constexpr uint32_t kNegInf = Elem<T>::kBf16 ? 0x007fu : 0x03ffu;
+        const uint32_t key = sample_key16(fresh(raw[j >> 1]) >> (16 * (j & 1)));
+        return key > kNegInf ? key : 0u;
+      }
+    };
+
+    // ---- zmax over the entries that take part ----
+    float zm = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < ne; ++j) {
+      const float z = z_of(j);
+      if constexpr (kStoreW) w[j] = z;
+      if (is_valid(j)) zm = fmaxf(zm, z);
+      __builtin_amdgcn_sched_barrier(0);  // one entry at a time (here and below): interleaving the unrolled bodies costs more registers than there are
+    }
+    zm = wave_max(zm);
+    if (lane == 0) s_fmax[wid] = zm;
+    __syncthreads();
+    float zmax = s_fmax[0];
+#pragma unroll
+    for (int i = 1; i < 16; ++i) zmax = fmaxf(zmax, s_fmax[i]);
+    const bool have_max = zmax > -INFINITY && zmax < INFINITY;
+    if constexpr (kStoreW) {
+#pragma unroll
+      for (int j = 0; j < ne; ++j) {
+        w[j] = (is_valid(j) && have_max) ? expf(w[j] - zmax) : 0.f;
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+    auto mass_of = [&](int j) -> uint64_t {
+      if constexpr (kStoreW) return sample_mass(__uint_as_float(fresh(__float_as_uint(w[j]))));
+      else return (is_valid(j) && have_max) ? sample_mass(expf(z_of(j) - zmax)) : 0ull;
+    };
+
+    // ---- radix descent: the smallest key >= lo whose inclusive ascending cumulative weight (over keys >= lo) exceeds thr ----
+    // mass == false: weight 1, thr = N - k (N = entries that take part): the k-th largest key.  mass == true: weight m, thr = floor(q * M).
+    auto select = [&](bool mass, uint32_t lo, uint64_t k, double q) -> uint32_t {
+      uint32_t prefix = 0, mask = 0;
+      uint64_t thr = 0;
+#pragma unroll
+      for (int lvl = 0; lvl < KB; ++lvl) {
+        const int shift = 8 * (KB - 1 - lvl);
+        for (int i = tid; i < 256 * kHistCopies; i += 1024) hist[i] = 0ull;
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < ne; ++j) {
+          const uint32_t key = key_of(j);
+          if (key >= lo && (key & mask) == prefix) {
+            const uint64_t wt = mass ? mass_of(j) : 1ull;
+            if (wt) atomicAdd(&hist[((key >> shift) & 255u) * kHistCopies + (lane & (kHistCopies - 1))], (unsigned long long)wt);
+          }
+          __builtin_amdgcn_sched_barrier(0);
+        }
+        __syncthreads();
+        if (tid < 256) {
+          unsigned long long s = 0;
+#pragma unroll
+          for (int c = 0; c < kHistCopies; ++c) s += hist[tid * kHistCopies + ((c + tid) & (kHistCopies - 1))];
+          red[tid] = s;
+        }
+        if (tid == 0) {  // (nobody reads these between here and the chooser below)
+          s_bin = 0;
+          s_thr = 0ull;
+        }
+        __syncthreads();
+        if (wid == 0) {
+          const uint64_t c0 = red[4 * lane], c1 = red[4 * lane + 1], c2 = red[4 * lane + 2], c3 = red[4 * lane + 3];
+          const uint64_t mine = c0 + c1 + c2 + c3;
+          const uint64_t incl = wave_scan_u64(mine, lane);
+          if (lvl == 0) {
+            const uint64_t total = (uint64_t)__shfl((unsigned long long)incl, 63, 64);
+            thr = mass ? (uint64_t)floor(q * (double)total) : (total > k ? total - k : 0ull);
+          }
+          const uint64_t excl = incl - mine;
+          if (excl <= thr && thr < incl) {  // exactly one lane when anything takes part
+            uint64_t a = excl;
+            int bin = 4 * lane;
+            if (thr < a + c0) bin = 4 * lane;
+            else if (thr < (a += c0) + c1) bin = 4 * lane + 1;
+            else if (thr < (a += c1) + c2) bin = 4 * lane + 2;
+            else { a += c2; bin = 4 * lane + 3; }
+            s_bin = bin;
+            s_thr = thr - a;
+          }
+        }
+        __syncthreads();
+        prefix |= (uint32_t)s_bin << shift;
+        mask |= 255u << shift;
+        thr = s_thr;
+      }
+      return prefix;
+    };
+
+    uint32_t lo = 1u;
+    if (top_k >= 1) {
+      const uint32_t kth = select(false, lo, (uint64_t)top_k, 0.0);
+      lo = kth > lo ? kth : lo;
+    }
+    if (top_p < 1.0f) {
+      const uint32_t pth = select(true, lo, 0ull, 1.0 - (double)top_p);
+      lo = pth > lo ? pth : lo;
+    }
+
+    // ---- the draw: 64-bit block scan of the kept masses in index order ----
+    uint64_t mine = 0;
+#pragma unroll
+    for (int j = 0; j < ne; ++j) {
+      if (key_of(j) >= lo) mine += mass_of(j);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    const uint64_t incl_w = wave_scan_u64(mine, lane);
+    __syncthreads();  // (s_wave is free: nothing above uses it; the barrier also orders the last select's shared reads before reuse)
+    if (lane == 63) s_wave[wid] = incl_w;
+    __syncthreads();
+    uint64_t before = 0, K = 0;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const uint64_t c = s_wave[i];
+      if (i < wid) before += c;
+      K += c;
+    }
+    const uint64_t excl = before + incl_w - mine;
+    uint32_t rnd[4];
+    philox4x32_10((uint32_t)cur_step, (uint32_t)(prm->row_base + b), 0u, 0u, prm->seed_lo, prm->seed_hi, rnd);
+    const uint64_t r64 = ((uint64_t)rnd[1] << 32) | (uint64_t)rnd[0];
+    const uint64_t t = __umul64hi(r64, K);  // < K
+    if (K > 0 && excl <= t && t < excl + mine) {  // exactly one thread
+      uint64_t acc = excl;
+      int n_le = 0;  // the prefix sums never decrease: the first entry whose sum exceeds t comes after exactly the entries whose sum does not
+#pragma unroll
+      for (int j = 0; j < ne; ++j) {
+        if (key_of(j) >= lo) acc += mass_of(j);
+        n_le = (int)fresh((uint32_t)(n_le + (acc <= t ? 1 : 0)));  // (settled here: left alone, the compares are sunk below the loop and every sum stays alive)
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      s_tok = tid * ne + (n_le < ne ? n_le : 0);
+    }
+    if (kept_mask) {
+      const int base = (int)fresh((uint32_t)(tid * ne));
+#pragma unroll
+      for (int j = 0; j < ne; ++j) {
+        const int v = base + j;
+        if (v < V) kept_mask[(int64_t)b * V + v] = key_of(j) >= lo ? 1 : 0;
+      }
+    }
+  }
+  __syncthreads();
+  if (tid == 0) {  // dl_decode_advance's bookkeeping, statement for statement
+    int tok = s_tok;
+    if (finished) {
+      if (st_fin) tok = pad_id;
+      else if (eos_id >= 0 && (tok == eos_id || tok == eos_id2 || tok == eos_id3)) finished[b] = 1;
+    }
+    next_ids[b] = tok;
+    if (out_ids && step) {
+      if (st_step < out_cap) out_ids[(int64_t)b * out_cap + st_step] = tok;
+      step[b] = st_step + 1;
+    }
+    if (kv_len_full) kv_len_full[b] = st_full + 1;
+    if (kv_len_sparse) kv_len_sparse[b] = st_sparse + st_dec;
+  }
+}
+
+}  // namespace dl
+
+using namespace dl;
+
+static_assert(sizeof(dl_sample_params) == sizeof(dl_sample_params_dev) && sizeof(dl_sample_params) == 32, "dl_sample_params layout");
+
+extern "C" int dl_decode_sample(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B, int64_t* next_ids, int64_t* out_ids,
+                                int out_cap, int32_t* step, int32_t* finished, int eos_id, int eos_id2, int eos_id3, int pad_id,
+                                int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision, int min_new_tokens,
+                                const dl_sample_params* params, uint8_t* kept_mask, void* stream) {
+  DL_REQUIRE(logits && next_ids, "dl_decode_sample: NULL pointer");
+  DL_REQUIRE(params, "dl_decode_sample: NULL parameter block");
+  DL_REQUIRE(B > 0 && V > 0, "dl_decode_sample: bad shape");
+  DL_REQUIRE(V <= kSampleMaxV, "dl_decode_sample: V=%d exceeds %d (64-bit fixed-point masses)", V, kSampleMaxV);
+  hipStream_t st = as_stream(stream);
+  const dl_sample_params_dev* prm = reinterpret_cast<const dl_sample_params_dev*>(params);
+  const int e2 = eos_id >= 0 ? eos_id2 : -1, e3 = eos_id >= 0 ? eos_id3 : -1;
+#define DL_SAMPLE_LAUNCH(T, R)                                                                                                                  \
+  hipLaunchKernelGGL((decode_sample_kernel<T, R>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, next_ids, out_ids, out_cap, \
+                     step, finished, eos_id, e2, e3, pad_id, kv_len_full, kv_len_sparse, decision, min_new_tokens, prm, kept_mask)
+  DL_DISPATCH_DTYPE(logits_dtype, T, {
+    if constexpr (Elem<T>::kVec == 8) {
+      if (V <= 1024 * 4 * 8) DL_SAMPLE_LAUNCH(T, 4);
+      else DL_SAMPLE_LAUNCH(T, 8);
+    } else {
+      DL_SAMPLE_LAUNCH(T, 0);
+    }
+  });
+#undef DL_SAMPLE_LAUNCH
+  DL_CHECK_LAUNCH("dl_decode_sample");
+  return DL_OK;
+}

@@ -75,6 +75,9 @@ class _DecodeState:
             self.qkv_parts = torch.empty(2 * B * (nH + 2 * nKV) * d, dtype=torch.float32, device=device)  # q|k|v's two k ranges, added by the attention launch
         self.o_parts = torch.empty(8 * B * H, dtype=torch.float32, device=device) if (self.use_smallm and not self.use_mx8_gemm and B <= 32 and getattr(l0, "wp_o", None) is not None) else None  # o_proj's k-range slices (dl_linear_tiles)
         self.graphs = {}  # captured decode steps, keyed by (slab, split factors, ...): see _run_decode_steps
+        # dl_decode_sample's parameter block (temperature, top-k, top-p, seed, row base): device memory the captured launches read, rewritten by
+        # generate() before the first launch of a sampled request -- one graph serves every setting
+        self.sample_params = ops.sample_params_block(device)
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
         self.tp_gran = ops.gemv_gu_tp_workspace(tpm.d_model, device) if (B == 1 and tpm is not None and dtype in (torch.bfloat16, torch.float16) and H <= 5120 and H % 8 == 0 and tpm.d_model % 32 == 0) else None
@@ -118,10 +121,16 @@ class DecodeScheduler:
         if advance:
             sc = self.config.sparse_config
             use_tp = bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and sc["sparse_layer"] < self.config.num_hidden_layers
-            ops.decode_advance(
-                st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
-                st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
-            )
+            if getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
+                ops.decode_sample(
+                    st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
+                    st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
+                )
+            else:
+                ops.decode_advance(
+                    st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
+                    st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
+                )
 
     def _decode_step_gemv(self, st: _DecodeState, cache: KVSlabCache):
         """Small-batch decode step: 5 weight-streaming launches per layer (dl_gemv with fused residual-add+RMSNorm /
@@ -395,7 +404,8 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch)
+               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
+               bool(getattr(self, "_sampled", False)))  # (sampled or greedy: which bookkeeping kernel was captured; the sampling parameters are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)
@@ -424,4 +434,7 @@ class DecodeScheduler:
             torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
         self._prefill_logits_buf.copy_(st.logits)
         # first token: argmax only (the prompt's KV lengths are already in place); EOS is banned while step < min_new (HF semantics)
-        ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)
+        if getattr(self, "_sampled", False):  # token 0 is drawn with step = 0
+            ops.decode_sample(st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)
+        else:
+            ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)

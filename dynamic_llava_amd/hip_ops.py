@@ -143,6 +143,10 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p],
     ),
+    "dl_decode_sample": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
+    ),
 }
 
 _lib = None
@@ -726,6 +730,51 @@ def decode_advance(logits, next_ids, out_ids=None, step=None, finished=None, eos
             _p(kv_len_full), _p(kv_len_sparse), _p(decision), int(min_new_tokens), _stream(),
         ),
         "dl_decode_advance",
+    )
+    return next_ids
+
+
+def sample_params_words(temperature, top_k=0, top_p=None, seed=0, row_base=0):
+    """dl_sample_params (include/dynllava.h) as a CPU int32 [8] tensor: copy it into the device block (`sample_params_block`) before the first launch of
+    a request.  Values as sampling.normalize_params takes them (temperature 0 / None = 1.0; top_k 0 = off; top_p None or >= 1 = off; bad values raise ValueError); seed: 64 bits; row_base: added to the row index in the Philox counter."""
+    import struct
+
+    from .sampling import normalize_params  # the one validator: generate() and this packer share its conventions (0 / None = off)
+
+    t, top_k, p = normalize_params(temperature, top_k, top_p)
+    p = 1.0 if p is None else p  # the kernel's "off"
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    raw = struct.pack("<fifIIiii", t, min(int(top_k), 2**31 - 1), p, s & 0xFFFFFFFF, s >> 32, int(row_base), 0, 0)
+    return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone()
+
+
+def sample_params_block(device):
+    """Device memory for one dl_sample_params (zeroed: write it with `block.copy_(sample_params_words(...))`)."""
+    return torch.zeros(8, dtype=torch.int32, device=device)
+
+
+def decode_sample(logits, next_ids, params, out_ids=None, step=None, finished=None, eos_id=-1, pad_id=0, kv_len_full=None, kv_len_sparse=None, decision=None, min_new_tokens=0,
+                  kept_mask=None):
+    """dl_decode_advance's bookkeeping around a sampled token (include/dynllava.h, sampling.py).  params: int32 [8] DEVICE tensor holding a dl_sample_params;
+    kept_mask: optional uint8 [B, V] debug output (1 = token in the kept set)."""
+    eos = [int(e) for e in eos_id] if isinstance(eos_id, (list, tuple)) else [int(eos_id)]
+    if len(eos) > 3:
+        raise HipOpsError("dl_decode_sample compares at most three eos ids on the device")
+    eos = (eos + [-1, -1, -1])[:3]
+    _dev(logits, next_ids, params, kept_mask)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
+    B, V = logits.shape
+    if params is not None:  # (None reaches the library, which refuses it)
+        assert params.dtype == torch.int32 and params.numel() >= 8 and params.is_contiguous()
+    if kept_mask is not None:
+        assert kept_mask.dtype == torch.uint8 and kept_mask.shape == (B, V) and kept_mask.is_contiguous()
+    out_cap = out_ids.shape[1] if out_ids is not None else 0
+    _check(
+        lib().dl_decode_sample(
+            _p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(next_ids), _p(out_ids), out_cap, _p(step), _p(finished), eos[0], eos[1], eos[2], int(pad_id),
+            _p(kv_len_full), _p(kv_len_sparse), _p(decision), int(min_new_tokens), _p(params), _p(kept_mask), _stream(),
+        ),
+        "dl_decode_sample",
     )
     return next_ids
 

@@ -33,6 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
+from . import sampling
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -344,6 +345,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "clip_tiles_gemm": getattr(self.get_vision_tower(), "tiles_gemm", None), "clip_tiles_max_batch": getattr(self.get_vision_tower(), "tiles_max_batch", None),
             "clip_tiles_ksplit": [getattr(self.get_vision_tower(), "tiles_ksplit_out", None), getattr(self.get_vision_tower(), "tiles_ksplit_fc2", None)],
             "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch,
+            "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }
@@ -587,24 +589,32 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         """dynamic_llava_llama.py:117-152: greedy decoding; returns the NEW tokens only [B, T_new] (HF behaviour when
         generation is driven by inputs_embeds).  Supported kwargs: max_new_tokens / max_length, min_new_tokens (EOS banned from
-        the argmax until then, as HF's MinNewTokensLengthLogitsProcessor), do_sample (True: temperature / top_k / top_p sampling
-        through _generate_sample), num_beams(1), use_cache(True), eos_token_id, pad_token_id, attention_mask,
+        the argmax until then, as HF's MinNewTokensLengthLogitsProcessor), do_sample (True: temperature / top_k / top_p sampling --
+        with seed=<int> on the device, inside the same captured graphs as greedy decoding (dl_decode_sample; the rule is sampling.py;
+        sample_row_base=<int> offsets the rows' random streams for sharded batches); without seed, or with generator=, through
+        _generate_sample on torch's RNG), num_beams(1), use_cache(True), eos_token_id, pad_token_id, attention_mask,
         return_dict_in_generate (+ output_scores), image_features (pre-computed projector output, testing).
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
         the new token ids / pixels into static buffers."""
         self._check_ready()
+        sampled = None  # (temperature, top_k, top_p, seed, row base) when the device sampler draws the tokens
         if kwargs.get("do_sample", False):  # model_vqa_loader.py:162-175 passes do_sample = temperature > 0 (default 0: greedy)
             if "inputs_embeds" in kwargs:
                 raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
-            return self._generate_sample(inputs, images, **kwargs)
+            if not sampling.device_route(kwargs, self.config.vocab_size, self.config.eos_token_id):  # (the EOS set resolved as _gen_kwargs resolves it)
+                return self._generate_sample(inputs, images, **kwargs)
+            # seed=<int>: the draw moves into the captured graphs (dl_decode_sample; the rule is sampling.py) and everything below is the greedy path's
+            # code.  The parameters are validated here, before any launch, and travel in device memory: no graph key knows them.
+            sampled = sampling.normalize_params(kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p")) + (int(kwargs["seed"]), int(kwargs.get("sample_row_base", 0) or 0))
         if kwargs.get("past_key_values") is not None:
             return self._generate_on_cache(inputs, images, **kwargs)
         attention_mask = kwargs.get("attention_mask")
         image_features = kwargs.get("image_features")
         sync_every = int(kwargs.get("sync_every", self.decode_sync_every))  # decode steps enqueued between two observations of the device state
         want_dict = bool(kwargs.get("return_dict_in_generate"))
-        want_scores = want_dict and bool(kwargs.get("output_scores"))
+        want_logits = want_dict and bool(kwargs.get("output_logits"))  # HF: the raw (unprocessed) logits of every step
+        want_scores = want_dict and (bool(kwargs.get("output_scores")) or want_logits)
         inputs = inputs.to(self.device)
         tm = None
         if self.record_timing:
@@ -653,6 +663,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._eos = -1 if eos is None else (tuple(eos) if isinstance(eos, list) else eos)  # one id or a tuple of up to three (the EOS set)
         self._pad = pad
         self._min_new = min_new
+        self._sampled = sampled is not None  # which bookkeeping kernel _first_token / the decode steps launch (and capture)
+        if sampled is not None:
+            st.sample_params.copy_(ops.sample_params_words(*sampled))
         if getattr(self, "_prefill_logits_buf", None) is None or self._prefill_logits_buf.shape != st.logits.shape:
             self._prefill_logits_buf = torch.empty(st.logits.shape, dtype=torch.float32, device=self.device)
         vp = getattr(self.model, "image_score_predictor", None)
@@ -665,7 +678,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
             key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
                    cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._eos, self._pad, min_new, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key())  # (a knob toggled at run time must not replay a graph captured under the other setting)
+                   self._prefill_knob_key(), self._sampled)  # (a knob toggled at run time must not replay a graph captured under the other setting)
             ent = self._prefill_graphs.get(key)
             if ent is None:
                 # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
@@ -743,12 +756,18 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if tm is not None:
             tm["ev"][1].record()
             tm["path"] = prefill_path
-        scores = []
+        scores, raw_logits = [], []
 
         eos_ids = [] if self._eos == -1 else (list(self._eos) if isinstance(self._eos, tuple) else [self._eos])
 
         def _score(step_idx):  # HF `scores`: the processed logits of that step (EOS at -inf while step < min_new_tokens)
             z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
+            if want_logits:
+                raw_logits.append(z.clone())
+            if sampled is not None:  # the processed logits of a sampled step: z = logit / T with -inf outside the kept set (sampling.py), as HF reports them
+                # (on the host side of the loop, with the contract's own arithmetic: this branch reads the step buffer after every step anyway)
+                scores.append(sampling.processed_logits(z.cpu(), sampled[0], sampled[1], sampled[2], eos_ids if step_idx < min_new else ()).to(z.device))
+                return
             if step_idx < min_new and eos_ids:
                 z[:, eos_ids] = float("-inf")
             scores.append(z)
@@ -817,6 +836,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 first = int(torch.argmax(all_done).item())
                 out = out[:, : first + 1]
                 scores = scores[: first + 1]
+                raw_logits = raw_logits[: first + 1]
         self.last_cache = cache
         if tm is not None:
             tm["ev"][2].record()
@@ -830,7 +850,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if ptr not in k}
             st.graphs = {k: v for k, v in st.graphs.items() if ptr not in k}
             res = {"sequences": out, "past_key_values": cache}
-            if want_scores:
+            if want_scores and kwargs.get("output_scores"):
                 res["scores"] = tuple(scores)
+            if want_logits:
+                res["logits"] = tuple(raw_logits)
             return res
         return out

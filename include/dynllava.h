@@ -324,6 +324,33 @@ int dl_decode_advance(const void* logits, int logits_dtype, int64_t logits_row_s
                       int eos_id, int eos_id2, int eos_id3, int pad_id, int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision,
                       int min_new_tokens, void* stream);
 
+/* ---- sampled decode step: dl_decode_advance with the argmax replaced by temperature / top-k / top-p sampling; the same bookkeeping,
+ * statement for statement (finished rows emit pad_id, the EOS set, out_ids / step / kv_len_*, the min_new_tokens ban).
+ * The rule, per row (dynamic_llava_amd/sampling.py states it in full and is what the kernel is tested against):
+ *   1. z = float32(logit) / temperature, a correctly rounded division; banned ids are out.
+ *   2. top_k >= 1: keep z >= (k-th largest z), ties at the threshold included.  top_k <= 0: off.
+ *   3. w = expf(z - zmax); m = floor(w * 2^40) as a 64-bit integer.  Every sum below is an integer sum (exact, order-independent).
+ *   4. top_p < 1: with M = sum of m over the survivors of 2 and thr = floor((1.0 - (double)top_p) * (double)M), keep v iff S(z_v) > thr,
+ *      S(x) = mass of the survivors with z <= x (a tie class stays whole).  top_p >= 1: off.
+ *   5. Philox4x32-10, key = (seed_lo, seed_hi), counter = (step[b], row_base + b, 0, 0); r64 = out[1] << 32 | out[0]; K = kept mass;
+ *      t = (r64 * K) >> 64; the token is the kept one of lowest index whose inclusive prefix sum of m (index order) exceeds t.
+ * params: DEVICE memory (one captured graph serves every setting; the host rewrites the block between requests).  temperature must be finite and > 0
+ * (the host validates: the kernel trusts the block).  A logit of -inf is treated like a banned id.
+ * logits: bf16 / fp16 / fp32, V <= 65536 (DL_ERR_ARG beyond).  kept_mask: uint8 [B, V] or NULL -- debug output, 1 where the token is in the
+ * kept set (rows that were already finished are not written). */
+typedef struct dl_sample_params {
+  float temperature;
+  int32_t top_k;
+  float top_p;
+  uint32_t seed_lo, seed_hi;
+  int32_t row_base;
+  int32_t reserved[2];
+} dl_sample_params;
+int dl_decode_sample(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
+                     int64_t* next_ids, int64_t* out_ids, int out_cap, int32_t* step, int32_t* finished,
+                     int eos_id, int eos_id2, int eos_id3, int pad_id, int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision,
+                     int min_new_tokens, const dl_sample_params* params, uint8_t* kept_mask, void* stream);
+
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
  * operand registers).  bf16 / f16, fp32 accumulate, one rounding.  K % 256 == 0, N % 4 == 0; ldx / ldy: row strides (elements).

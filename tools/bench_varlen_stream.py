@@ -19,6 +19,9 @@ ap.add_argument("--requests", type=int, default=200)
 ap.add_argument("--new-tokens", type=int, default=128)
 ap.add_argument("--fixed", action="store_true")
 ap.add_argument("--layers", type=int, default=32)
+ap.add_argument("--temperature", type=float, default=0.0, help="> 0: sample (the reference's own scripts default to 0.2); 0: greedy, the call this tool always made")
+ap.add_argument("--top-p", type=float, default=None)
+ap.add_argument("--seed", type=int, default=None, help="with --temperature > 0: sample on the device (dl_decode_sample inside the captured graphs); without it torch's RNG and the plain loop")
 args = ap.parse_args()
 
 dev, dt = torch.device("cuda"), torch.bfloat16
@@ -38,9 +41,10 @@ warm = torch.cat([torch.tensor([1]), torch.randint(3, cfg.vocab_size, (34,), gen
 model.generate(warm, images=images[0], max_new_tokens=4, eos_token_id=2)
 torch.cuda.synchronize()
 recs = []
+sample_kw = dict(do_sample=False) if args.temperature <= 0 else dict(do_sample=True, temperature=args.temperature, top_p=args.top_p, **({} if args.seed is None else {"seed": args.seed}))
 t0 = time.perf_counter()
 for i, ids in enumerate(reqs):
-    out = model.generate(ids, images=images[i % 8], max_new_tokens=args.new_tokens, do_sample=False, num_beams=1, use_cache=True, eos_token_id=2)
+    out = model.generate(ids, images=images[i % 8], max_new_tokens=args.new_tokens, num_beams=1, use_cache=True, eos_token_id=2, **sample_kw)
     n_out = int(out.shape[1])  # the harness decodes the ids on the host right away (VQAL:177): same synchronisation point
     recs.append((model.last_timing, ids.shape[1], n_out))
 torch.cuda.synchronize()

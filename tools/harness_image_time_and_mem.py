@@ -24,6 +24,9 @@ def main(argv=None):
     ap.add_argument("--keep-rate", type=float, default=0.2)
     ap.add_argument("--layers", type=int, default=None, help="debug: fewer layers")
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--temperature", type=float, default=0.0, help="> 0: sample (the reference's own scripts default to 0.2); 0: greedy, the call this tool always made")
+    ap.add_argument("--top-p", type=float, default=None)
+    ap.add_argument("--seed", type=int, default=None, help="with --temperature > 0: sample on the device (dl_decode_sample inside the captured graphs); without it torch's RNG and the plain loop")
     ap.add_argument("--result-file", default=None)
     ap.add_argument("--no-operand-copies", action="store_true", help="build without the operand-order weight copies (decoder dl_linear_packed, CLIP / projector "
                     "dl_linear_tiles): `model memory` then equals the reference's figure for the same checkpoint (the parameters), at the library GEMMs' speed")
@@ -72,7 +75,8 @@ def main(argv=None):
     for _ in range(args.reps):
         with torch.inference_mode():
             start_event.record()
-            outputs = model.generate(input_ids, images=images_tensor, image_sizes=[(s, s)] * args.batch_size, do_sample=False, num_beams=1,
+            sample_kw = dict(do_sample=False) if args.temperature <= 0 else dict(do_sample=True, temperature=args.temperature, top_p=args.top_p, **({} if args.seed is None else {"seed": args.seed}))
+            outputs = model.generate(input_ids, images=images_tensor, image_sizes=[(s, s)] * args.batch_size, num_beams=1, **sample_kw,
                                      use_cache=True, output_scores=True, return_dict_in_generate=True, min_new_tokens=1, max_new_tokens=1)
             end_event.record()
             torch.cuda.synchronize()
