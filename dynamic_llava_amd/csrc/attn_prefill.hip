@@ -1399,27 +1399,75 @@ __global__ __launch_bounds__(256) void attn_prefill_simple_kernel(const void* __
   }
 }
 
+// ---- which kernel answers a bf16 / f16 call: ONE pure host function (dl_attn_prefill_route exports it), the launch below switches on its value.
+// Thresholds and their measurements; the DL_PF_* switches are for tuning experiments and A/B runs only.
+//  * waves of the plain / pipelined kernels (tools/bench_attn_prefill.py): 2 waves (32 query rows) per workgroup win for short rows (more workgroups,
+//    16-180 us range), 4 waves for long ones; 1 wave never wins (each workgroup then stages whole K/V tiles alone)
+//  * the software-pipelined kernel wins once rows span several K/V tiles (T=631: 61 -> 46 us; B=32 T=700: 974 -> 708 us), is a wash at T=170 (3 tiles,
+//    latency of the dependent S -> softmax -> PV chain dominates) and loses at B=32 T=215, where 3 resident workgroups per CU hide the loads better than
+//    one double-buffered one (head_dim 64 -- CLIP, the vision predictor -- stays on the plain kernel: 31.6 vs 34.6 us at T=577, its tiles are too small
+//    to pay for the second buffer)
+//  * K/V tile size of the plain kernel: 128 keys for the head_dim-64 towers (CLIP T=577: 27.3 -> 22 us per layer), else 64.  (One 192-key tile for the
+//    T=170 decoder rows was no faster at B=1 -- 15.4 vs 15.1 us -- and 2x slower at B=8: 116 KB of LDS, one workgroup per CU.)
+//  * key-split kernel (one workgroup per CU: 90-120 KB of LDS): fresh prefill while the launch fits the chip in a single round of workgroups -- at larger
+//    batches the plain kernel's three resident workgroups per CU win.
+//      head_dim 128, causal, 64 < rows <= 192 (decoder layers >= 2 at B=1): 32 rows x (2 | 3) key tiles, one round  (T=170: 15.2 -> 8.9 us)
+//      head_dim 64, full, rows > 128 (CLIP tower, vision predictor): 64 rows x 4 key tiles, rounds of 256 keys
+//  * whole-row kernel, head_dim 64 (round 6): all keys of a head on chip in fragment order, no rounds (CLIP tower: 17.4 -> see
+//    profiles/r06_attn_whole_row.txt); many (image, head) pairs: one 16-wave workgroup per pair, every fragment read feeding two or three query tiles
+//    (tools/bench_attn_prefill_batched.py --clip)
+//  * whole-head kernel, head_dim 128 (late round 6): the compacted layers of a prefill -- one workgroup per (request, head).
+//    tools/bench_attn_prefill_batched.py, 158..214 rows, us: 32 requests 47.8 (plain kernel 140.0), 8: 16.7 (54.1), 4: 13.3 (33.5), 2: 11.4 (24.0), and
+//    even ONE request's 32 workgroups on 32 CUs 8.6 against the key-split kernel's 192 workgroups 9.7 (T = 170); two workgroups per head up to
+//    DL_PF_WHOLE128_ZPAIRS (request, head) pairs: 1 request 8.6 -> 7.2 us, 2: 11.5 -> 8.5, 4: 13.2 -> 9.7; 8: 16.7 -> 19.2 (one per head stays)
+static int pf_route_16bit(int D, int B, int max_seqlen, int n_heads, int causal, bool cached, int64_t q_rs, int64_t kv_rs, int64_t out_rs) {
+  int nw = max_seqlen <= 256 ? 2 : 4;
+  if (const char* e = getenv("DL_PF_NW")) nw = atoi(e) == 1 ? 1 : (atoi(e) == 2 ? 2 : 4);
+  bool pipe = max_seqlen > 256 && D == 128;
+  if (const char* e = getenv("DL_PF_PIPE")) pipe = atoi(e) != 0;
+  const int bn = (D == 64 && max_seqlen > 128) ? 128 : 64;
+  if (D == 64) {
+    bool whole = !causal && !cached && max_seqlen > 256 && max_seqlen <= 608 && q_rs % 8 == 0 && kv_rs % 8 == 0 && out_rs % 4 == 0 &&
+                 (int64_t)max_seqlen * kv_rs * 2 < ((int64_t)1 << 31);
+    if (const char* e = getenv("DL_PF_WHOLE")) whole = whole && atoi(e) != 0;  // A/B against the key-split kernel
+    if (whole) {
+      static const int head_pairs = getenv("DL_PF_HEAD64_MIN") ? atoi(getenv("DL_PF_HEAD64_MIN")) : 256;
+      if ((int64_t)B * n_heads >= head_pairs) return DL_PF_HEAD_D64;
+      int kwv = 4;
+      if (const char* e = getenv("DL_PF_WHOLE_KW")) kwv = atoi(e) == 2 ? 2 : 4;
+      return kwv == 2 ? DL_PF_WHOLE_ROW_D64_KW2 : DL_PF_WHOLE_ROW_D64_KW4;
+    }
+  }
+  if (D == 128) {
+    static const int min_pairs = getenv("DL_PF_WHOLE128_MIN") ? atoi(getenv("DL_PF_WHOLE128_MIN")) : 1;  // (tuning: tools/bench_attn_prefill_batched.py)
+    bool whole = causal && !cached && max_seqlen > 64 && max_seqlen <= 256 && (int64_t)B * n_heads >= min_pairs && q_rs % 8 == 0 && kv_rs % 8 == 0 && out_rs % 4 == 0 &&
+                 (int64_t)max_seqlen * kv_rs * 2 < ((int64_t)1 << 31);
+    if (const char* e = getenv("DL_PF_WHOLE128")) whole = whole && atoi(e) != 0;  // A/B against the plain kernel
+    if (whole) {
+      static const int z_pairs = getenv("DL_PF_WHOLE128_ZPAIRS") ? atoi(getenv("DL_PF_WHOLE128_ZPAIRS")) : 128;
+      return ((int64_t)B * n_heads <= z_pairs) ? DL_PF_WHOLE_D128_Z2 : DL_PF_WHOLE_D128_Z1;
+    }
+  }
+  if (D == 128 || D == 64) {
+    bool ksplit = false;
+    if (D == 128) ksplit = causal && !cached && max_seqlen > 64 && max_seqlen <= 192 && (int64_t)B * n_heads * ((max_seqlen + 31) / 32) <= 256;
+    if (D == 64) ksplit = !causal && !cached && max_seqlen > 128 && (int64_t)B * n_heads * ((max_seqlen + 63) / 64) <= 256;
+    if (const char* e = getenv("DL_PF_KSPLIT")) ksplit = ksplit && atoi(e) != 0;
+    if (ksplit) return D == 64 ? DL_PF_KSPLIT_D64 : (max_seqlen <= 128 ? DL_PF_KSPLIT_D128_K2 : DL_PF_KSPLIT_D128_K3);
+  }
+  if (pipe && nw > 1) return nw == 4 ? DL_PF_PIPE_4W : DL_PF_PIPE_2W;
+  if (nw == 4) return (D == 64 && bn == 128) ? DL_PF_PLAIN_4W_K128 : DL_PF_PLAIN_4W;
+  return nw == 2 ? DL_PF_PLAIN_2W : DL_PF_PLAIN_1W;
+}
+
 template <typename T, int D>
-static void launch_mfma(const void* q, const void* k, const void* v, int64_t q_rs, int64_t kv_rs, void* out, int64_t out_rs,
+static void launch_mfma(int route, const void* q, const void* k, const void* v, int64_t q_rs, int64_t kv_rs, void* out, int64_t out_rs,
                         const int32_t* cu, int B, int max_seqlen, int n_heads, int n_rep, int causal, hipStream_t st,
                         const int32_t* kv_len = nullptr, int64_t kv_sb = 0, int64_t kv_sh = 0) {
   const float scale = 1.0f / sqrtf((float)D);
-  // tools/bench_attn_prefill.py: 2 waves (32 query rows) per workgroup win for short rows (more workgroups, 16-180 us range),
-  // 4 waves for long ones; 1 wave never wins (each workgroup then stages whole K/V tiles alone)
-  int nw = max_seqlen <= 256 ? 2 : 4;
-  if (const char* e = getenv("DL_PF_NW")) nw = atoi(e) == 1 ? 1 : (atoi(e) == 2 ? 2 : 4);  // tuning experiments only
-  // tools/bench_attn_prefill.py: the software-pipelined kernel wins once rows span several K/V tiles (T=631: 61 -> 46 us;
-  // B=32 T=700: 974 -> 708 us), is a wash at T=170 (3 tiles, latency of the dependent S -> softmax -> PV chain dominates) and loses
-  // at B=32 T=215, where 3 resident workgroups per CU hide the loads better than one double-buffered one
-  // (head_dim 64 -- CLIP, the vision predictor -- stays on the plain kernel: 31.6 vs 34.6 us at T=577, its tiles are too small to pay
-  // for the second buffer)
-  bool pipe = max_seqlen > 256 && D == 128;
-  if (const char* e = getenv("DL_PF_PIPE")) pipe = atoi(e) != 0;  // tuning experiments only
-  // K/V tile size of the plain kernel: 128 keys for the head_dim-64 towers (CLIP T=577: 27.3 -> 22 us per layer), else 64.  (One 192-key
-  // tile for the T=170 decoder rows was no faster at B=1 -- 15.4 vs 15.1 us -- and 2x slower at B=8: 116 KB of LDS, one workgroup per CU.)
-  const int bn = (D == 64 && max_seqlen > 128) ? 128 : 64;
-#define DL_LAUNCH_PLAIN_BN(NWV, CAUS, BNV)                                                                                               \
+#define DL_LAUNCH_PLAIN(NWV, CAUS, BNV)                                                                                                  \
   {                                                                                                                                      \
+    const dim3 grid((unsigned)((max_seqlen + 16 * NWV - 1) / (16 * NWV)), (unsigned)n_heads, (unsigned)B);                              \
     const size_t smem = (size_t)(BNV * (D + kPad) + D * (BNV + kPad) + NWV * 16 * (BNV + kPad)) * 2;                                     \
     auto kfn = attn_prefill_mfma_kernel<T, D, CAUS, NWV, BNV>;                                                                           \
     static bool attr_set = false;                                                                                                        \
@@ -1429,59 +1477,21 @@ static void launch_mfma(const void* q, const void* k, const void* v, int64_t q_r
     }                                                                                                                                    \
     hipLaunchKernelGGL(kfn, grid, dim3(NWV * 64), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale, kv_len, kv_sb, kv_sh);   \
   }
-#define DL_LAUNCH_PLAIN(NWV, CAUS)                                                                                                       \
-  {                                                                                                                                      \
-    bool done = false;                                                                                                                   \
-    if constexpr (D == 64 && NWV == 4) {                                                                                                 \
-      if (bn == 128) {                                                                                                                   \
-        DL_LAUNCH_PLAIN_BN(4, CAUS, 128) done = true;                                                                                    \
-      }                                                                                                                                  \
-    }                                                                                                                                    \
-    if (!done) DL_LAUNCH_PLAIN_BN(NWV, CAUS, 64)                                                                                         \
-  }
-#define DL_LAUNCH_PF(NWV, CAUS)                                                                                                          \
+#define DL_LAUNCH_PIPE(NWV, CAUS)                                                                                                        \
   {                                                                                                                                      \
     const dim3 grid((unsigned)((max_seqlen + 16 * NWV - 1) / (16 * NWV)), (unsigned)n_heads, (unsigned)B);                              \
-    if (pipe && NWV > 1) {                                                                                                               \
-      const size_t smem = (size_t)(2 * (kBN * (D + kPad) + D * (kBN + kPad)) + NWV * 16 * (kBN + kPad)) * 2;                             \
-      auto kfn = attn_prefill_mfma_pipe_kernel<T, D, CAUS, (NWV > 1 ? NWV : 2)>;                                                         \
-      static bool attr_set = false;                                                                                                      \
-      if (!attr_set && smem > 64 * 1024) {                                                                                               \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);           \
-        attr_set = true;                                                                                                                 \
-      }                                                                                                                                  \
-      hipLaunchKernelGGL(kfn, grid, dim3(NWV * 64), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale, kv_len, kv_sb, kv_sh); \
-    } else {                                                                                                                             \
-      DL_LAUNCH_PLAIN(NWV, CAUS)                                                                                                         \
+    const size_t smem = (size_t)(2 * (kBN * (D + kPad) + D * (kBN + kPad)) + NWV * 16 * (kBN + kPad)) * 2;                               \
+    auto kfn = attn_prefill_mfma_pipe_kernel<T, D, CAUS, NWV>;                                                                           \
+    static bool attr_set = false;                                                                                                        \
+    if (!attr_set && smem > 64 * 1024) {                                                                                                 \
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);             \
+      attr_set = true;                                                                                                                   \
     }                                                                                                                                    \
+    hipLaunchKernelGGL(kfn, grid, dim3(NWV * 64), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale, kv_len, kv_sb, kv_sh);   \
   }
-  // key-split kernel (one workgroup per CU: 90-120 KB of LDS): fresh prefill while the launch fits the chip in a single round of
-  // workgroups -- at larger batches the plain kernel's three resident workgroups per CU win.
-  //   head_dim 128, causal, 64 < rows <= 192 (decoder layers >= 2 at B=1): 32 rows x (2 | 3) key tiles, one round  (T=170: 15.2 -> 8.9 us)
-  //   head_dim 64, full, rows > 128 (CLIP tower, vision predictor): 64 rows x 4 key tiles, rounds of 256 keys
-  if constexpr (D == 64) {
-    // whole-row kernel (round 6): all keys of a head on chip in fragment order, no rounds (CLIP tower: 17.4 -> see profiles/r06_attn_whole_row.txt)
-    bool whole = !causal && !kv_len && max_seqlen > 256 && max_seqlen <= 608 && q_rs % 8 == 0 && kv_rs % 8 == 0 && out_rs % 4 == 0 &&
-                 (int64_t)max_seqlen * kv_rs * 2 < ((int64_t)1 << 31);
-    if (const char* e = getenv("DL_PF_WHOLE")) whole = whole && atoi(e) != 0;  // A/B against the key-split kernel
-    if (whole) {
-      const size_t smem = (size_t)(38 * 2 + 4 * 19) * 1024;
-      // many (image, head) pairs: one 16-wave workgroup per pair, every fragment read feeding two or three query tiles (tools/bench_attn_prefill_batched.py --clip)
-      static const int head_pairs = getenv("DL_PF_HEAD64_MIN") ? atoi(getenv("DL_PF_HEAD64_MIN")) : 256;
-      if ((int64_t)B * n_heads >= head_pairs) {
-        auto kfn = attn_prefill_head_d64_kernel<T>;
-        static bool attr_set = false;
-        if (!attr_set) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-          attr_set = true;
-        }
-        hipLaunchKernelGGL(kfn, dim3((unsigned)n_heads, (unsigned)B), dim3(1024), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale);
-        return;
-      }
-      int kwv = 4;
-      if (const char* e = getenv("DL_PF_WHOLE_KW")) kwv = atoi(e) == 2 ? 2 : 4;  // tuning experiments only
 #define DL_LAUNCH_WHOLE(KWV)                                                                                                             \
   {                                                                                                                                      \
+    const size_t smem = (size_t)(38 * 2 + 4 * 19) * 1024;                                                                                \
     auto kfn = attn_prefill_whole_d64_kernel<T, KWV>;                                                                                    \
     static bool attr_set = false;                                                                                                        \
     if (!attr_set) {                                                                                                                     \
@@ -1491,39 +1501,6 @@ static void launch_mfma(const void* q, const void* k, const void* v, int64_t q_r
     hipLaunchKernelGGL(kfn, dim3((unsigned)((max_seqlen + 63) / 64), (unsigned)n_heads, (unsigned)B), dim3(256 * KWV), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, \
                        n_rep, scale);                                                                                                    \
   }
-      if (kwv == 2) DL_LAUNCH_WHOLE(2) else DL_LAUNCH_WHOLE(4)
-#undef DL_LAUNCH_WHOLE
-      return;
-    }
-  }
-  if constexpr (D == 128) {
-    // whole-head kernel (late round 6): the compacted layers of a prefill -- one workgroup per (request, head).  tools/bench_attn_prefill_batched.py, 158..214 rows, us:
-    // 32 requests 47.8 (plain kernel 140.0), 8: 16.7 (54.1), 4: 13.3 (33.5), 2: 11.4 (24.0), and even ONE request's 32 workgroups on 32 CUs 8.6 against the key-split
-    // kernel's 192 workgroups 9.7 (T = 170); with two workgroups per head at <= 128 pairs (below): 7.2 / 8.5 / 9.7 at one / two / four requests
-    static const int min_pairs = getenv("DL_PF_WHOLE128_MIN") ? atoi(getenv("DL_PF_WHOLE128_MIN")) : 1;  // (tuning: tools/bench_attn_prefill_batched.py)
-    bool whole = causal && !kv_len && max_seqlen > 64 && max_seqlen <= 256 && (int64_t)B * n_heads >= min_pairs && q_rs % 8 == 0 && kv_rs % 8 == 0 && out_rs % 4 == 0 &&
-                 (int64_t)max_seqlen * kv_rs * 2 < ((int64_t)1 << 31);
-    if (const char* e = getenv("DL_PF_WHOLE128")) whole = whole && atoi(e) != 0;  // A/B against the plain kernel
-    if (whole) {
-      const size_t smem = (size_t)(16 * 4 + 8 * 8) * 1024;
-      auto kfn = attn_prefill_whole_d128_causal_kernel<T>;
-      static bool attr_set = false;
-      if (!attr_set) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
-        attr_set = true;
-      }
-      static const int z_pairs = getenv("DL_PF_WHOLE128_ZPAIRS") ? atoi(getenv("DL_PF_WHOLE128_ZPAIRS")) : 128;  // two workgroups per head up to this many (request, head) pairs: 1 request 8.6 -> 7.2 us, 2: 11.5 -> 8.5, 4: 13.2 -> 9.7; 8: 16.7 -> 19.2 (one per head stays)
-      const unsigned zs = ((int64_t)B * n_heads <= z_pairs) ? 2u : 1u;
-      hipLaunchKernelGGL(kfn, dim3((unsigned)n_heads, (unsigned)B, zs), dim3(512), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale);
-      return;
-    }
-  }
-  if constexpr (D == 128 || D == 64) {
-    bool ksplit = false;
-    if (D == 128) ksplit = causal && !kv_len && max_seqlen > 64 && max_seqlen <= 192 && (int64_t)B * n_heads * ((max_seqlen + 31) / 32) <= 256;
-    if (D == 64) ksplit = !causal && !kv_len && max_seqlen > 128 && (int64_t)B * n_heads * ((max_seqlen + 63) / 64) <= 256;
-    if (const char* e = getenv("DL_PF_KSPLIT")) ksplit = ksplit && atoi(e) != 0;  // tuning experiments only
-    if (ksplit) {
 #define DL_LAUNCH_KS(CAUS, RWV, KWV)                                                                                                     \
   {                                                                                                                                      \
     const dim3 grid((unsigned)((max_seqlen + 16 * RWV - 1) / (16 * RWV)), (unsigned)n_heads, (unsigned)B);                              \
@@ -1536,58 +1513,134 @@ static void launch_mfma(const void* q, const void* k, const void* v, int64_t q_r
     }                                                                                                                                    \
     hipLaunchKernelGGL(kfn, grid, dim3(RWV * KWV * 64), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale);                  \
   }
-      if constexpr (D == 128) {
-        if (max_seqlen <= 128) DL_LAUNCH_KS(true, 2, 2) else DL_LAUNCH_KS(true, 2, 3)
-      } else {
-        DL_LAUNCH_KS(false, 4, 4)
+#define DL_BY_MASK(LAUNCH, ...)                                                                                                          \
+  {                                                                                                                                      \
+    if (causal) LAUNCH(__VA_ARGS__, true) else LAUNCH(__VA_ARGS__, false)                                                                \
+  }
+#define DL_PLAIN_C(NWV, BNV, CAUS) DL_LAUNCH_PLAIN(NWV, CAUS, BNV)
+#define DL_PIPE_C(NWV, CAUS) DL_LAUNCH_PIPE(NWV, CAUS)
+  switch (route) {
+    case DL_PF_PLAIN_1W: DL_BY_MASK(DL_PLAIN_C, 1, 64) break;
+    case DL_PF_PLAIN_2W: DL_BY_MASK(DL_PLAIN_C, 2, 64) break;
+    case DL_PF_PLAIN_4W: DL_BY_MASK(DL_PLAIN_C, 4, 64) break;
+    case DL_PF_PLAIN_4W_K128:
+      if constexpr (D == 64) DL_BY_MASK(DL_PLAIN_C, 4, 128)
+      break;
+    case DL_PF_PIPE_2W: DL_BY_MASK(DL_PIPE_C, 2) break;
+    case DL_PF_PIPE_4W: DL_BY_MASK(DL_PIPE_C, 4) break;
+    case DL_PF_KSPLIT_D128_K2:
+      if constexpr (D == 128) DL_LAUNCH_KS(true, 2, 2)
+      break;
+    case DL_PF_KSPLIT_D128_K3:
+      if constexpr (D == 128) DL_LAUNCH_KS(true, 2, 3)
+      break;
+    case DL_PF_KSPLIT_D64:
+      if constexpr (D == 64) DL_LAUNCH_KS(false, 4, 4)
+      break;
+    case DL_PF_WHOLE_ROW_D64_KW2:
+      if constexpr (D == 64) DL_LAUNCH_WHOLE(2)
+      break;
+    case DL_PF_WHOLE_ROW_D64_KW4:
+      if constexpr (D == 64) DL_LAUNCH_WHOLE(4)
+      break;
+    case DL_PF_HEAD_D64:
+      if constexpr (D == 64) {
+        const size_t smem = (size_t)(38 * 2 + 4 * 19) * 1024;
+        auto kfn = attn_prefill_head_d64_kernel<T>;
+        static bool attr_set = false;
+        if (!attr_set) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+          attr_set = true;
+        }
+        hipLaunchKernelGGL(kfn, dim3((unsigned)n_heads, (unsigned)B), dim3(1024), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale);
       }
+      break;
+    case DL_PF_WHOLE_D128_Z1:
+    case DL_PF_WHOLE_D128_Z2:
+      if constexpr (D == 128) {
+        const size_t smem = (size_t)(16 * 4 + 8 * 8) * 1024;
+        auto kfn = attn_prefill_whole_d128_causal_kernel<T>;
+        static bool attr_set = false;
+        if (!attr_set) {
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kfn), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+          attr_set = true;
+        }
+        const unsigned zs = route == DL_PF_WHOLE_D128_Z2 ? 2u : 1u;
+        hipLaunchKernelGGL(kfn, dim3((unsigned)n_heads, (unsigned)B, zs), dim3(512), smem, st, q, k, v, q_rs, kv_rs, out, out_rs, cu, n_rep, scale);
+      }
+      break;
+    default: break;  // (pf_route_16bit returns nothing else)
+  }
+#undef DL_PIPE_C
+#undef DL_PLAIN_C
+#undef DL_BY_MASK
 #undef DL_LAUNCH_KS
-      return;
-    }
-  }
-  if (causal) {
-    if (nw == 4) DL_LAUNCH_PF(4, true) else if (nw == 2) DL_LAUNCH_PF(2, true) else DL_LAUNCH_PF(1, true)
-  } else {
-    if (nw == 4) DL_LAUNCH_PF(4, false) else if (nw == 2) DL_LAUNCH_PF(2, false) else DL_LAUNCH_PF(1, false)
-  }
-#undef DL_LAUNCH_PF
+#undef DL_LAUNCH_WHOLE
+#undef DL_LAUNCH_PIPE
 #undef DL_LAUNCH_PLAIN
-#undef DL_LAUNCH_PLAIN_BN
 }
 
 }  // namespace dl
 
 using namespace dl;
 
+// The argument checks and the choice of kernel of both entry points (`who` = NULL: dl_attn_prefill_route asks, nothing is reported through dl_last_error()).
+// Returns a DL_PF_* value or DL_ERR_ARG.
+static int pf_route(const char* who, int B, int max_seqlen, int max_kv_len, int n_heads, int n_kv_heads, int head_dim, int causal, bool cached,
+                    int64_t q_row_stride, int64_t kv_row_stride, int64_t out_row_stride, int dtype) {
+#define DL_PF_REQUIRE(cond, ...)          \
+  do {                                    \
+    if (!(cond)) {                        \
+      if (who) set_error(__VA_ARGS__);    \
+      return DL_ERR_ARG;                  \
+    }                                     \
+  } while (0)
+  DL_PF_REQUIRE(B > 0 && max_seqlen >= 0 && n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0, "%s: bad shape", who);
+  if (max_seqlen == 0) return DL_PF_NONE;  // an empty input is a no-op, whatever its (possibly NULL) pointers
+  if (dtype == DL_F32) {
+    DL_PF_REQUIRE(head_dim > 0 && head_dim <= 256, "%s: head_dim=%d unsupported for f32", who, head_dim);
+    DL_PF_REQUIRE(max_kv_len <= 8192, "%s: f32 path supports up to 8192 keys", who);
+    return DL_PF_SIMPLE_F32;
+  }
+  if (dtype == DL_F16 || dtype == DL_BF16) {
+    DL_PF_REQUIRE(head_dim == 32 || head_dim == 64 || head_dim == 128, "%s: head_dim=%d unsupported (32, 64 or 128)", who, head_dim);
+    DL_PF_REQUIRE(q_row_stride % 8 == 0 && kv_row_stride % 8 == 0, "%s: row strides must be multiples of 8 elements", who);
+    return pf_route_16bit(head_dim, B, max_seqlen, n_heads, causal, cached, q_row_stride, kv_row_stride, out_row_stride);
+  }
+  DL_PF_REQUIRE(false, "%s: unsupported dtype %d", who, dtype);
+#undef DL_PF_REQUIRE
+  return DL_ERR_ARG;
+}
+
 static int attn_prefill_impl(const char* who, const void* q, const void* k, const void* v, int64_t q_row_stride, int64_t kv_row_stride,
                              void* out, int64_t out_row_stride, const int32_t* cu_seqlens, int B, int max_seqlen, int max_kv_len, int n_heads,
                              int n_kv_heads, int head_dim, int causal, int dtype, void* stream, const int32_t* kv_len, int64_t kv_sb,
                              int64_t kv_sh) {
-  DL_REQUIRE(B > 0 && max_seqlen >= 0 && n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0, "%s: bad shape", who);
-  if (max_seqlen == 0) return DL_OK;  // an empty input is a no-op, whatever its (possibly NULL) pointers
+  const int route = pf_route(who, B, max_seqlen, max_kv_len, n_heads, n_kv_heads, head_dim, causal, kv_len != nullptr, q_row_stride, kv_row_stride,
+                             out_row_stride, dtype);
+  if (route < 0) return route;
+  if (route == DL_PF_NONE) return DL_OK;
   DL_REQUIRE(q && k && v && out && cu_seqlens, "%s: NULL pointer", who);
   hipStream_t st = as_stream(stream);
   const int n_rep = n_heads / n_kv_heads;
-  if (dtype == DL_F32) {
-    DL_REQUIRE(head_dim > 0 && head_dim <= 256, "%s: head_dim=%d unsupported for f32", who, head_dim);
-    DL_REQUIRE(max_kv_len <= 8192, "%s: f32 path supports up to 8192 keys", who);
+  if (route == DL_PF_SIMPLE_F32) {
     const size_t smem = (size_t)(4 * head_dim + 4 * (size_t)max_kv_len) * sizeof(float);
+    static size_t smem_allowed = 64 * 1024;  // rows of more than ~4000 keys need the opt-in (8192 keys x 4 waves: 132 KB of the CU's 160)
+    if (smem > smem_allowed) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(attn_prefill_simple_kernel<f32_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem);
+      smem_allowed = smem;
+    }
     hipLaunchKernelGGL((attn_prefill_simple_kernel<f32_t>), dim3((unsigned)((max_seqlen + 3) / 4), (unsigned)n_heads, (unsigned)B),
                        dim3(256), smem, st, q, k, v, q_row_stride, kv_row_stride, out, out_row_stride, cu_seqlens, n_rep,
                        1.0f / sqrtf((float)head_dim), head_dim, causal, max_kv_len, kv_len, kv_sb, kv_sh);
-  } else if (dtype == DL_F16 || dtype == DL_BF16) {
-    DL_REQUIRE(head_dim == 32 || head_dim == 64 || head_dim == 128, "%s: head_dim=%d unsupported (32, 64 or 128)", who, head_dim);
-    DL_REQUIRE(q_row_stride % 8 == 0 && kv_row_stride % 8 == 0, "%s: row strides must be multiples of 8 elements", who);
-#define DL_PF_ARGS q, k, v, q_row_stride, kv_row_stride, out, out_row_stride, cu_seqlens, B, max_seqlen, n_heads, n_rep, causal, st, kv_len, kv_sb, kv_sh
+  } else {
+#define DL_PF_ARGS route, q, k, v, q_row_stride, kv_row_stride, out, out_row_stride, cu_seqlens, B, max_seqlen, n_heads, n_rep, causal, st, kv_len, kv_sb, kv_sh
     if (dtype == DL_BF16) {
       if (head_dim == 128) launch_mfma<bf16_t, 128>(DL_PF_ARGS); else if (head_dim == 64) launch_mfma<bf16_t, 64>(DL_PF_ARGS); else launch_mfma<bf16_t, 32>(DL_PF_ARGS);
     } else {
       if (head_dim == 128) launch_mfma<f16_t, 128>(DL_PF_ARGS); else if (head_dim == 64) launch_mfma<f16_t, 64>(DL_PF_ARGS); else launch_mfma<f16_t, 32>(DL_PF_ARGS);
     }
 #undef DL_PF_ARGS
-  } else {
-    set_error("%s: unsupported dtype %d", who, dtype);
-    return DL_ERR_ARG;
   }
   DL_CHECK_LAUNCH(who);
   return DL_OK;
@@ -1608,4 +1661,13 @@ extern "C" int dl_attn_prefill_cached(const void* q, int64_t q_row_stride, const
   DL_REQUIRE(max_kv_len >= max_seqlen, "dl_attn_prefill_cached: max_kv_len must bound kv_len[b] + row length");
   return attn_prefill_impl("dl_attn_prefill_cached", q, k_slab, v_slab, q_row_stride, head_dim, out, out_row_stride, cu_seqlens, B, max_seqlen,
                            max_kv_len, n_heads, n_kv_heads, head_dim, 1, dtype, stream, kv_len, slab_stride_b, slab_stride_h);
+}
+
+extern "C" int dl_attn_prefill_route(int B, int max_seqlen, int max_kv_len, int n_heads, int n_kv_heads, int head_dim, int causal, int cached,
+                                     int64_t q_row_stride, int64_t kv_row_stride, int64_t out_row_stride, int dtype) {
+  if (cached) {  // dl_attn_prefill_cached's own checks and the arguments it hands on: causal, slab rows head_dim elements apart
+    if (max_kv_len < max_seqlen) return DL_ERR_ARG;
+    return pf_route(nullptr, B, max_seqlen, max_kv_len, n_heads, n_kv_heads, head_dim, 1, true, q_row_stride, head_dim, out_row_stride, dtype);
+  }
+  return pf_route(nullptr, B, max_seqlen, max_seqlen, n_heads, n_kv_heads, head_dim, causal, false, q_row_stride, kv_row_stride, out_row_stride, dtype);
 }

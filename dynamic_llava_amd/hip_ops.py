@@ -65,6 +65,7 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     ),
+    "dl_attn_prefill_route": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int]),
     "dl_attn_decode_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "dl_attn_decode": (
         c_int,
@@ -324,6 +325,19 @@ def attn_prefill_cached(q, k_slab, v_slab, kv_len, out, cu_seqlens, max_seqlen, 
         "dl_attn_prefill_cached",
     )
     return out
+
+
+# include/dynllava.h DL_PF_*: the kernel a prefill attention call runs (attn_prefill_route)
+PF_ROUTES = ("NONE", "SIMPLE_F32", "PLAIN_1W", "PLAIN_2W", "PLAIN_4W", "PLAIN_4W_K128", "PIPE_2W", "PIPE_4W", "KSPLIT_D128_K2", "KSPLIT_D128_K3", "KSPLIT_D64",
+             "WHOLE_ROW_D64_KW2", "WHOLE_ROW_D64_KW4", "HEAD_D64", "WHOLE_D128_Z1", "WHOLE_D128_Z2")
+
+
+def attn_prefill_route(B, max_seqlen, max_kv_len, n_heads, n_kv_heads, head_dim, causal, cached, q_row_stride, kv_row_stride, out_row_stride, dtype):
+    """Name (PF_ROUTES) of the kernel attn_prefill (cached False) / attn_prefill_cached (cached True) launches for these arguments -- the launch's own
+    decision, DL_PF_* environment switches included; None for arguments the launch refuses.  Host only: needs the library, not a GPU."""
+    r = lib().dl_attn_prefill_route(int(B), int(max_seqlen), int(max_kv_len), n_heads, n_kv_heads, head_dim, 1 if causal else 0, 1 if cached else 0,
+                                    int(q_row_stride), int(kv_row_stride), int(out_row_stride), dtype_code(dtype))
+    return PF_ROUTES[r] if r >= 0 else None
 
 
 def attn_decode_workspace(B, n_heads, head_dim, n_splits, device):

@@ -104,6 +104,32 @@ int dl_attn_prefill_cached(const void* q, int64_t q_row_stride, const void* k_sl
                            const int32_t* cu_seqlens, int B, int max_seqlen, int max_kv_len, int n_heads, int n_kv_heads,
                            int head_dim, int dtype, void* stream);
 
+/* Which kernel dl_attn_prefill (cached = 0; max_kv_len is ignored) or dl_attn_prefill_cached (cached != 0; causal and kv_row_stride are ignored) runs for
+ * these arguments: the launch's own decision -- same code, same DL_PF_* environment switches -- as a pure host query.  Returns a DL_PF_* value, or DL_ERR_ARG
+ * for arguments the launch would refuse (dl_last_error() is left alone).  Tests assert with it that a shape still reaches the kernel it was written for.
+ * (no existing argument list changed: the ABI version stays) */
+enum {
+  DL_PF_NONE = 0,             /* max_seqlen == 0: nothing is enqueued */
+  DL_PF_SIMPLE_F32 = 1,       /* fp32: one wave per query row */
+  DL_PF_PLAIN_1W = 2,         /* MFMA, 64-key tiles, 1 / 2 / 4 waves of 16 query rows per workgroup */
+  DL_PF_PLAIN_2W = 3,
+  DL_PF_PLAIN_4W = 4,
+  DL_PF_PLAIN_4W_K128 = 5,    /* head_dim 64: 128-key tiles */
+  DL_PF_PIPE_2W = 6,          /* software-pipelined (double-buffered K/V tiles) */
+  DL_PF_PIPE_4W = 7,
+  DL_PF_KSPLIT_D128_K2 = 8,   /* key-split: head_dim 128 causal, 32 rows x 2 | 3 key tiles */
+  DL_PF_KSPLIT_D128_K3 = 9,
+  DL_PF_KSPLIT_D64 = 10,      /* head_dim 64 full, 64 rows x 4 key tiles */
+  DL_PF_WHOLE_ROW_D64_KW2 = 11, /* head_dim 64 full, 257..608 rows: whole row on chip, 2 | 4 key waves */
+  DL_PF_WHOLE_ROW_D64_KW4 = 12,
+  DL_PF_HEAD_D64 = 13,        /* the same rows, one 16-wave workgroup per (image, head) pair */
+  DL_PF_WHOLE_D128_Z1 = 14,   /* head_dim 128 causal, 65..256 rows: one | two workgroups per (request, head) */
+  DL_PF_WHOLE_D128_Z2 = 15,
+  DL_PF_ROUTE_COUNT = 16
+};
+int dl_attn_prefill_route(int B, int max_seqlen, int max_kv_len, int n_heads, int n_kv_heads, int head_dim, int causal, int cached,
+                          int64_t q_row_stride, int64_t kv_row_stride, int64_t out_row_stride, int dtype);
+
 /* ---- F9 (decode) + F11: one query token per row against the ragged KV slab (DML:1061-1122 with
  * CU:256-268).  Row b attends keys [0, kv_len[b] + extra) of its slab; q: [B, q_row_stride].
  * Split-KV: `n_splits` workgroups per (row, head); partials in `workspace` (float), merged by a
