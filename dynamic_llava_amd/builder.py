@@ -86,15 +86,16 @@ def _load_checkpoint_tensors(model_path):
 
 @torch.no_grad()
 def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bit=False, load_4bit=False, device_map="auto", device="cuda", use_flash_attn=False, torch_dtype=None,
-                          decode_weight_format=None, decode_weight_max_batch=None, **kwargs):
+                          decode_weight_format=None, decode_weight_max_batch=None, kv_cache_format=None, **kwargs):
     """dynamic_llava_builder.py:35-249.  Returns (tokenizer, model, image_processor, context_len).
     decode_weight_format: None or "mxfp8" (model.set_decode_weight_format: the decoder's projection weights become their MXFP8 values W' in the model dtype and
     the small-batch decode step streams the FP8 codes); decode_weight_max_batch: its max_batch (decode steps of up to that many rows, at most 32, stream the
-    codes through dl_gemm_mx8).  load_8bit / load_4bit (bitsandbytes' numerics) stay unsupported."""
+    codes through dl_gemm_mx8).  kv_cache_format: None or "mxfp8" (model.set_kv_cache_format: the kept keys / values are stored as MXFP8 codes).  load_8bit / load_4bit (bitsandbytes' numerics) stay unsupported."""
     if decode_weight_format not in (None, "mxfp8"):
         raise ValueError(f"decode_weight_format={decode_weight_format!r}: expected None or 'mxfp8'")
-    from .mxfp8 import check_decode_weight_format
+    from .mxfp8 import check_decode_weight_format, check_kv_cache_format
 
+    check_kv_cache_format(kv_cache_format)
     check_decode_weight_format(decode_weight_format, decode_weight_max_batch, 1)  # before anything is loaded; against the model's gemv_max_decode_batch below
     if load_8bit or load_4bit:
         raise NotImplementedError("bitsandbytes quantised loading (BLD:51-62) is out of scope for the MI355X hot path")
@@ -158,6 +159,7 @@ def load_pretrained_model(model_path, model_base=None, model_name=None, load_8bi
     check_decode_weight_format(decode_weight_format, decode_weight_max_batch, model.gemv_max_decode_batch)
     model.decode_weight_format = decode_weight_format
     model.mx8_max_decode_batch = decode_weight_max_batch
+    model.kv_cache_format = kv_cache_format
     model.finalize()
     context_len = cfg.extra.get("max_sequence_length", 2048)
     return tokenizer, model, image_processor, context_len

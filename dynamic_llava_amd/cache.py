@@ -40,8 +40,7 @@ class _LayerViews:
             i += c.n_layers
         if not 0 <= i < c.n_layers:
             raise KeyError(f"Cache only has {c.n_layers} layers, attempted to access layer with index {i}")
-        T = c.padded_length(i)
-        return (c.k[i][:, :, :T, :], c.v[i][:, :, :T, :])
+        return c.legacy_layer(i, c.padded_length(i))
 
     def __iter__(self):
         for i in range(len(self)):
@@ -54,6 +53,8 @@ _SINGLE_SPLIT_MAX_KEYS = int(os.environ.get("DL_SINGLE_SPLIT_MAX_KEYS", "256"))
 
 
 class KVSlabCache:
+    kv_format = None  # storage format of the kept keys / values: None = the model dtype; "mxfp8": KVSlabCacheMX8
+
     def __init__(self, n_layers, sparse_layer, batch, n_kv_heads, head_dim, t_cap, dtype, device):
         self.n_layers = n_layers
         self.sparse_layer = sparse_layer
@@ -63,10 +64,7 @@ class KVSlabCache:
         self.t_cap = int(t_cap)
         self.dtype = dtype
         self.device = device
-        # one allocation for all layers: [L, 2, B, nKV, T_cap, d]
-        self.slab = torch.empty((n_layers, 2, batch, n_kv_heads, self.t_cap, head_dim), dtype=dtype, device=device)
-        self.k = [self.slab[i, 0] for i in range(n_layers)]
-        self.v = [self.slab[i, 1] for i in range(n_layers)]
+        self._allocate(self.t_cap)
         # lens[0] = layers < sparse_layer, lens[1] = layers >= sparse_layer
         self.lens = torch.zeros((2, batch), dtype=torch.int32, device=device)
         # exact host mirror of lens[0] (advances by one per token for every row) -> capacity checks without a sync
@@ -90,6 +88,29 @@ class KVSlabCache:
         self.single_split_max_keys = _SINGLE_SPLIT_MAX_KEYS
         self.fused_single_keys = 256  # see fused_attn_splits
         self.min_keys_per_split = 64  # a split workgroup is given at least this many keys (tests lower it to force split launches on tiny rows)
+
+    def _allocate(self, t_cap: int, keep_rows: int = 0):
+        """(Re-)allocate the storage for `t_cap` slots per row; the first `keep_rows` slots keep their contents."""
+        # one allocation for all layers: [L, 2, B, nKV, T_cap, d]
+        new = torch.empty((self.n_layers, 2, self.batch, self.n_kv_heads, t_cap, self.head_dim), dtype=self.dtype, device=self.device)
+        if keep_rows:
+            new[:, :, :, :, :keep_rows, :] = self.slab[:, :, :, :, :keep_rows, :]
+        self.slab = new
+        self.k = [self.slab[i, 0] for i in range(self.n_layers)]
+        self.v = [self.slab[i, 1] for i in range(self.n_layers)]
+
+    def nbytes(self) -> int:
+        """Bytes of the K/V storage (all layers)."""
+        return self.slab.numel() * self.slab.element_size()
+
+    def legacy_layer(self, i: int, T: int):
+        """(K, V) of layer i, model dtype, [B, nKV, T, d]: what the legacy tuple shows."""
+        return (self.k[i][:, :, :T, :], self.v[i][:, :, :T, :])
+
+    def _store_rows(self, i: int, k: torch.Tensor, v: torch.Tensor):
+        """Import model-dtype rows k / v [B, nKV, T, d] into slots [0, T) of layer i."""
+        self.k[i][:, :, : k.shape[2], :] = k.to(self.device)
+        self.v[i][:, :, : v.shape[2], :] = v.to(self.device)
 
     def n_splits(self, layer_idx: int, rows_times_heads: int, max_splits: int = 32) -> int:
         """Split-KV factor of the decode attention (tools/bench_attn_decode.py sweep): enough workgroups to cover the 256 CUs
@@ -200,14 +221,10 @@ class KVSlabCache:
         if need <= self.t_cap:
             return False
         new_cap = max(need, int(self.t_cap * 1.5) + 16)
-        new = torch.empty((self.n_layers, 2, self.batch, self.n_kv_heads, new_cap, self.head_dim), dtype=self.dtype, device=self.device)
-        new[:, :, :, :, : self.t_cap, :] = self.slab
-        self.slab = new
+        self._allocate(new_cap, keep_rows=self.t_cap)
         self.sparse_cap += new_cap - self.t_cap
         self.logical_cap += new_cap - self.t_cap
         self.t_cap = new_cap
-        self.k = [self.slab[i, 0] for i in range(self.n_layers)]
-        self.v = [self.slab[i, 1] for i in range(self.n_layers)]
         return True
 
     # ---- reference-compatible surface ----
@@ -243,7 +260,12 @@ class KVSlabCache:
 
     # ---- import of a genuine legacy tuple (e.g. produced by the reference / oracle) ----
     @classmethod
-    def from_legacy_cache(cls, pkv, sparse_layer, t_cap_extra=256, device=None):  # cache_utils.py:304-318
+    def from_legacy_cache(cls, pkv, sparse_layer, t_cap_extra=256, device=None, kv_format=None):  # cache_utils.py:304-318
+        """kv_format "mxfp8": the imported rows are quantised with the host rule (mxfp8.quantize_mx8) into a KVSlabCacheMX8."""
+        if kv_format not in (None, "mxfp8"):
+            raise ValueError(f"KV cache format {kv_format!r}: expected None or 'mxfp8'")
+        if kv_format == "mxfp8" and cls.kv_format != "mxfp8":
+            return KVSlabCacheMX8.from_legacy_cache(pkv, sparse_layer, t_cap_extra, device, kv_format)
         layers, lens = pkv[0], pkv[1]
         L = len(layers)
         k0 = layers[0][0]
@@ -252,11 +274,81 @@ class KVSlabCache:
         tmax = max(int(layers[i][0].shape[2]) for i in range(L))
         c = cls(L, sparse_layer, B, nKV, d, tmax + t_cap_extra, k0.dtype, device)
         for i in range(L):
-            k, v = layers[i]
-            c.k[i][:, :, : k.shape[2], :] = k.to(device)
-            c.v[i][:, :, : v.shape[2], :] = v.to(device)
+            c._store_rows(i, *layers[i])
         c.lens[0] = torch.as_tensor(lens[0]).to(device=device, dtype=torch.int32)
         c.lens[1] = torch.as_tensor(lens[L - 1]).to(device=device, dtype=torch.int32)
         c.full_len_host = [int(x) for x in torch.as_tensor(lens[0]).tolist()]
         c.seen_tokens = max(c.full_len_host)
         return c
+
+
+class KVSlabCacheMX8(KVSlabCache):
+    """The slab in the MXFP8 format of mxfp8.py applied along head_dim (opt-in: model.set_kv_cache_format("mxfp8")): e4m3fn codes and one E8M0 scale byte per 32
+    consecutive elements of a key / value row, d + d/32 bytes per row instead of 2 d (0.516 of a 16-bit slab at d = 128).  Keys are stored after RoPE; lengths, eviction
+    and the decode schedule are the base class's.  `dtype` stays the MODEL dtype (its e_min clamps the block exponent, so every dequantised element is exact in it).
+
+      slab    uint8 [L, 2, B, nKV, T_cap, d]      codes;  k[i] / v[i]: the per-layer planes
+      scales  uint8 [L, 2, B, nKV, T_cap, d/32]   ks[i] / vs[i]
+
+    Written by dl_kv_quantize_mx8 (prefill) and dl_attn_decode_rope_kv8 (decode); the legacy view pkv[0][l] is dequantised on demand (mxfp8.dequantize_mx8, where the
+    planes live)."""
+
+    kv_format = "mxfp8"
+
+    def __init__(self, n_layers, sparse_layer, batch, n_kv_heads, head_dim, t_cap, dtype, device):
+        from . import mxfp8
+
+        if head_dim % mxfp8.BLOCK != 0:
+            raise ValueError(f"MXFP8 KV cache: head_dim={head_dim} is not a multiple of {mxfp8.BLOCK}")
+        mxfp8.e_min(dtype)  # raises for a model dtype the format is not defined for
+        self._scratch = None
+        super().__init__(n_layers, sparse_layer, batch, n_kv_heads, head_dim, t_cap, dtype, device)
+
+    def _allocate(self, t_cap: int, keep_rows: int = 0):
+        shape = (self.n_layers, 2, self.batch, self.n_kv_heads, t_cap)
+        codes = torch.empty(shape + (self.head_dim,), dtype=torch.uint8, device=self.device)
+        scales = torch.empty(shape + (self.head_dim // 32,), dtype=torch.uint8, device=self.device)
+        if keep_rows:
+            codes[:, :, :, :, :keep_rows, :] = self.slab[:, :, :, :, :keep_rows, :]
+            scales[:, :, :, :, :keep_rows, :] = self.scales[:, :, :, :, :keep_rows, :]
+        self.slab, self.scales = codes, scales
+        self.k = [codes[i, 0] for i in range(self.n_layers)]
+        self.v = [codes[i, 1] for i in range(self.n_layers)]
+        self.ks = [scales[i, 0] for i in range(self.n_layers)]
+        self.vs = [scales[i, 1] for i in range(self.n_layers)]
+        self._scratch = None
+
+    def nbytes(self) -> int:
+        return self.slab.numel() + self.scales.numel()
+
+    def prefill_scratch(self):
+        """One layer's model-dtype K / V slab [B, nKV, T_cap, d] each: dl_rope_kv_write's target during a prefill, quantised into the layer's planes right after
+        (dl_kv_quantize_mx8) and reused by the next layer -- 1/L of the model-dtype slab."""
+        if self._scratch is None:
+            self._scratch = torch.empty((2, self.batch, self.n_kv_heads, self.t_cap, self.head_dim), dtype=self.dtype, device=self.device)
+        return self._scratch[0], self._scratch[1]
+
+    def release_scratch(self):
+        """Free the prefill scratch (a later prefill on this cache allocates it again).  Not while a captured prefill graph holds its pointer."""
+        self._scratch = None
+
+    def _dequant(self, codes, scales, T):
+        from . import mxfp8
+
+        B, nKV, d = self.batch, self.n_kv_heads, self.head_dim
+        q = codes[:, :, :T, :].reshape(-1, d)
+        s = scales[:, :, :T, :].reshape(-1, d // 32)
+        return mxfp8.dequantize_mx8(q, s, self.dtype).reshape(B, nKV, T, d)
+
+    def legacy_layer(self, i: int, T: int):
+        return (self._dequant(self.k[i], self.ks[i], T), self._dequant(self.v[i], self.vs[i], T))
+
+    def _store_rows(self, i: int, k: torch.Tensor, v: torch.Tensor):
+        from . import mxfp8
+
+        d = self.head_dim
+        for x, codes, scales in ((k, self.k[i], self.ks[i]), (v, self.v[i], self.vs[i])):
+            T = x.shape[2]
+            q, s = mxfp8.quantize_mx8(x.to(self.device).reshape(-1, d), self.dtype)
+            codes[:, :, :T, :] = q.reshape(self.batch, self.n_kv_heads, T, d)
+            scales[:, :, :T, :] = s.reshape(self.batch, self.n_kv_heads, T, d // 32)

@@ -155,18 +155,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
   }
 }
 
-constexpr int kMaxSplits = 128;
-
-// Merge the split partials of one (row, head).  The partials were written by other CUs a microsecond ago, so every dependent
-// load is a full fabric round trip: all (m, l, o) values of up to 8 splits are requested at once (attn_split_merge).
-template <typename T, int D>
-__global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float* __restrict__ ws, void* __restrict__ out_,
-                                                                int64_t out_row_stride, int n_splits) {
-  const int h = blockIdx.x, b = blockIdx.y, n_heads = gridDim.x, d = threadIdx.x;
-  float o[1];
-  attn_split_merge<1>(ws + ((int64_t)b * n_heads + h) * n_splits * (D + kAttnPartPad), n_splits, D, d, o);
-  store1<T>(out_, (int64_t)b * out_row_stride + (int64_t)h * D + d, o[0]);
-}
+// (kMaxSplits and attn_decode_combine_kernel, the merge of the split partials, live in attn_decode_body.h: attn_decode_kv8.hip launches the same kernel)
 
 // workgroups of `kfn` (block threads, dynamic LDS bytes) the current device holds at once, at most 4 per CU (the regime the spin-wait of the
 // in-kernel combine was validated in); 0 when the device cannot be queried.  Cached per (kernel, device).

@@ -26,6 +26,20 @@ __device__ long long g_qa_stamps[1200][8];
 #endif
 
 
+constexpr int kMaxSplits = 128;
+
+// Merge the split partials of one (row, head).  The partials were written by other CUs a microsecond ago, so every dependent
+// load is a full fabric round trip: all (m, l, o) values of up to 8 splits are requested at once (attn_split_merge).
+// Launched by attn_decode.hip and by attn_decode_kv8.hip (the MXFP8 KV cache writes the same workspace layout).
+template <typename T, int D>
+__global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float* __restrict__ ws, void* __restrict__ out_,
+                                                                int64_t out_row_stride, int n_splits) {
+  const int h = blockIdx.x, b = blockIdx.y, n_heads = gridDim.x, d = threadIdx.x;
+  float o[1];
+  attn_split_merge<1>(ws + ((int64_t)b * n_heads + h) * n_splits * (D + kAttnPartPad), n_splits, D, d, o);
+  store1<T>(out_, (int64_t)b * out_row_stride + (int64_t)h * D + d, o[0]);
+}
+
 template <typename T, bool UPPER>
 __device__ __forceinline__ void rope16(const float (&own)[Elem<T>::kVec], const float (&par)[Elem<T>::kVec], const float (&cs)[Elem<T>::kVec],
                                        const float (&sn)[Elem<T>::kVec], float (&out)[Elem<T>::kVec]) {

@@ -13,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from .cache import KVSlabCache
+from .cache import KVSlabCache, KVSlabCacheMX8
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
 
@@ -161,7 +161,7 @@ class DecodeScheduler:
             # results are bit-identical to them WHEN the stand-alone attention also runs four waves (KVSlabCache.eight_wave_single_split =
             # False, as the kernel tests set it); by default the stand-alone single-split launch of a small batch runs eight waves -- another
             # (equally valid) summation order, so DL_FUSE_QKV_ATTN=0 is an A/B of speed, not of bits (tokens / KV lengths: tested equal)
-            fused_attn = self.fuse_qkv_attn and st.B == 1 and ns == 1 and st.qa_gran is not None
+            fused_attn = self.fuse_qkv_attn and st.B == 1 and ns == 1 and st.qa_gran is not None and cache.kv_format is None
             if fused_attn:
                 ops.gemv_qkv_attn(layer.w_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
                                   st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
@@ -187,8 +187,7 @@ class DecodeScheduler:
             # F8+F10+F9: RoPE, KV append at slot len[b] and ragged attention in one launch (1024-thread workgroups; split-KV
             # only when the row is long enough to need more than one workgroup per head)
             if not fused_attn:
-                ops.attn_decode_rope(st.qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH), chunk_keys=cache.spec_chunk(ns),
-                                     call_tag=(i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
+                self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
             ops.gemv(layer.self_attn.o_proj.weight, st.o, x=st.attn)
             if fused_tp:
                 tp = self.model.output_text_score_predictor
@@ -202,6 +201,32 @@ class DecodeScheduler:
         ops.gemv(self.lm_head.weight, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
         if use_tp and self.tp_side_stream:
             torch.cuda.current_stream().wait_stream(st.tp_stream)  # join before anything reads st.decision
+
+    def _attn_decode_rope(self, st, cache, i, qkv, lens, ns, call_tag):
+        """F8+F10+F9 of one decode layer: RoPE, KV append at slot len[b] and ragged split-KV attention, qkv [B, (nH+2nKV)*d] -> st.attn.  THE place that knows the
+        cache's storage format: model-dtype slabs run dl_attn_decode_rope, an MXFP8 cache (KVSlabCacheMX8) dl_attn_decode_rope_kv8 -- same schedule (split factor,
+        speculative chunk, four / eight waves); a lane holds 16 codes instead of 8 elements, so its trips request twice the keys (the same bytes); no in-launch merge."""
+        cfg = self.config
+        nH, nKV, d = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
+        cos, sin = self._rope
+        kif = cache.keys_in_flight(ns, st.B * nH)
+        if cache.kv_format == "mxfp8":
+            ops.attn_decode_rope_kv8(qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.ks[i], cache.v[i], cache.vs[i], st.attn, st.attn_ws, ns, nH, nKV, d,
+                                     keys_in_flight=2 * kif, chunk_keys=cache.spec_chunk(ns))
+        else:
+            ops.attn_decode_rope(qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=kif, chunk_keys=cache.spec_chunk(ns),
+                                 call_tag=call_tag)
+
+    def _kv_format_key(self, cache):
+        """What a captured graph depends on beyond the code / slab pointer: the cache's storage format and its scale allocation."""
+        sc = getattr(cache, "scales", None)
+        return (cache.kv_format, None if sc is None else sc.data_ptr())
+
+    def _new_cache(self, B, t_cap):
+        """A KV cache in the model's storage format (set_kv_cache_format)."""
+        cfg = self.config
+        cls = KVSlabCacheMX8 if self.kv_cache_format == "mxfp8" else KVSlabCache
+        return cls(cfg.num_hidden_layers, cfg.sparse_config["sparse_layer"], B, cfg.num_key_value_heads, cfg.head_dim, int(t_cap), self.dtype, self.device)
 
     def _decode_layer_mx8(self, st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp):
         """One layer of _decode_step_gemv on MXFP8 weights: the unfused launch sequence of the model-dtype step with dl_gemv_mx8 in place of dl_gemv.
@@ -223,8 +248,7 @@ class DecodeScheduler:
             else:
                 self.model.output_text_score_predictor.decide(h_cur, st.tp_ws, st.tp_logits, st.decision)
         L = cfg.num_hidden_layers
-        ops.attn_decode_rope(st.qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH),
-                             chunk_keys=cache.spec_chunk(ns), call_tag=(i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
+        self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
         ops.gemv_mx8(*m["o"], st.o, x=st.attn)
         ops.gemv_mx8(*m["gu"], st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps)
         ops.gemv_mx8(*m["down"], st.dn, x=st.gu)
@@ -258,7 +282,7 @@ class DecodeScheduler:
             if st.use_mx8_gemm:
                 self._decode_layer_gemm_mx8(st, cache, i, layer, lens, ns, tag)
                 continue
-            if lp_qkv and qkv_parts and cache.keys_in_flight(ns, st.B * nH) == 64:
+            if lp_qkv and qkv_parts and cache.keys_in_flight(ns, st.B * nH) == 64 and cache.kv_format is None:
                 # round 6 (verdict r5 item 2c): the projection's two k ranges stay fp32 partial sums and the RoPE / append / attention launch adds them (each (row, head)
                 # workgroup the 3 x head_dim values it reads): no hand-over inside the projection's launch.  In the step (profiles/r06_decode_qkv_parts.txt): the
                 # projection 22.7 -> 20.5 us at 32 rows; the attention launch pays for the wider loads in front of its first score (24.3 -> 28.2 us in the first build,
@@ -272,8 +296,7 @@ class DecodeScheduler:
                                             x_packed_mk=(st.B, st.h.shape[1]))
                 else:
                     qkv = ops.gemm_smallm(st.x, layer.w_qkv, out=st.qkv, workspace=ws, n_slices=self.smallm_wide_slices) if sm else F.linear(st.x, layer.w_qkv)
-                ops.attn_decode_rope(qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH), chunk_keys=cache.spec_chunk(ns),
-                                     call_tag=tag)
+                self._attn_decode_rope(st, cache, i, qkv, lens, ns, tag)
             nw = self.model.norm.weight if i + 1 == L else self.model.layers[i + 1].input_layernorm.weight
             lp = st.use_lp_mlp
             x_mlp = st.x_pk if lp else st.x  # the packed MLP reads its input in fragment order: the norm launch writes it that way
@@ -321,8 +344,7 @@ class DecodeScheduler:
         cos, sin = self._rope
         m, ws = layer.mx8, st.mx8_ws
         ops.gemm_mx8(st.x, *m["qkv"], out=st.qkv, workspace=ws)
-        ops.attn_decode_rope(st.qkv, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i], st.attn, st.attn_ws, ns, nH, nKV, d, keys_in_flight=cache.keys_in_flight(ns, st.B * nH),
-                             chunk_keys=cache.spec_chunk(ns), call_tag=tag)
+        self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, tag)
         parts, _ = ops.gemm_mx8_parts(st.attn, *m["o"], ws)
         ops.add_rmsnorm_parts(st.h, parts, layer.post_attention_layernorm.weight, eps, out=st.x)
         parts, _ = ops.gemm_mx8_parts(st.x, *m["gu"], ws)
@@ -335,13 +357,13 @@ class DecodeScheduler:
         """generate() owns its cache, so the slab is reused across calls: stable pointers keep the captured hipGraphs valid."""
         cfg = self.config
         c = getattr(self, "_cache_pool", None)
-        if c is None or c.batch != B or c.t_cap < t_need or c.dtype != self.dtype or c.sparse_layer != cfg.sparse_config["sparse_layer"]:
+        if c is None or c.batch != B or c.t_cap < t_need or c.dtype != self.dtype or c.sparse_layer != cfg.sparse_config["sparse_layer"] or c.kv_format != self.kv_cache_format:
             # slots are allocated in steps of 128: a stream of requests of slightly different lengths (VQAL:123-196) keeps ONE slab -- and with it
             # every captured graph that holds pointers into it -- instead of re-allocating whenever a prompt is a few tokens longer than any before
             old_ptr = None if c is None else c.slab.data_ptr()
             c = None
             self._cache_pool = None
-            c = KVSlabCache(cfg.num_hidden_layers, cfg.sparse_config["sparse_layer"], B, cfg.num_key_value_heads, cfg.head_dim, -(-int(t_need) // 128) * 128, self.dtype, self.device)
+            c = self._new_cache(B, -(-int(t_need) // 128) * 128)
             self._cache_pool = c
             if old_ptr is not None:  # graphs captured on the slab that has just been freed can never be replayed again
                 self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if old_ptr not in k}
@@ -365,7 +387,7 @@ class DecodeScheduler:
         from .cache import _SINGLE_SPLIT_MAX_KEYS
         if self.single_split_keys_override is not None:  # tests: force the schedule to change inside a short generation
             return int(self.single_split_keys_override), int(self.single_split_keys_override)
-        if not (self.fuse_qkv_attn and st.B == 1 and st.use_gemv and st.qa_gran is not None) or self.decode_weight_format == "mxfp8":
+        if not (self.fuse_qkv_attn and st.B == 1 and st.use_gemv and st.qa_gran is not None) or self.decode_weight_format == "mxfp8" or self.kv_cache_format == "mxfp8":
             return _SINGLE_SPLIT_MAX_KEYS, _SINGLE_SPLIT_MAX_KEYS
         w = self.model.layers[0].w_qkv
         big = (w.numel() * w.element_size()) >= 130e6  # 13B-class stream
@@ -405,7 +427,7 @@ class DecodeScheduler:
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
                self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
-               bool(getattr(self, "_sampled", False)))  # (sampled or greedy: which bookkeeping kernel was captured; the sampling parameters are device data, not part of the key)
+               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)))  # (sampled or greedy: which bookkeeping kernel was captured; the sampling parameters are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)

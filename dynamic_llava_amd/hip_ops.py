@@ -79,6 +79,15 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p],
     ),
+    "dl_kv_quantize_mx8": (
+        c_int,
+        [c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p],
+    ),
+    "dl_attn_decode_rope_kv8": (
+        c_int,
+        [c_void_p, c_int64, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_int64, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+         c_void_p],
+    ),
     "dl_topk_select": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "dl_compact_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_float, c_void_p, c_int, c_void_p]),
     "dl_linear": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p]),
@@ -390,6 +399,49 @@ def attn_decode_rope_parts(qkv_parts, cos, sin, pos_base, kv_len, k_slab, v_slab
             k_slab.stride(1), k_slab.shape[2], _p(out), out.stride(0), _p(workspace), int(n_splits), int(chunk_keys), int(call_tag), B, n_heads, n_kv_heads, head_dim, dtype_code(out.dtype), _stream(),
         ),
         "dl_attn_decode_rope_parts",
+    )
+    return out
+
+
+def _kv8_planes(kq, ks, vq, vs, head_dim):
+    for t in (kq, ks, vq, vs):
+        assert t.dtype == torch.uint8 and t.dim() == 4 and t.stride(3) == 1
+    assert kq.stride() == vq.stride() and ks.stride() == vs.stride() and kq.stride(2) == head_dim and ks.stride(2) == head_dim // 32
+    assert kq.stride(0) == 32 * ks.stride(0) and kq.stride(1) == 32 * ks.stride(1) and kq.shape[2] == ks.shape[2]
+
+
+def kv_quantize_mx8(k_src, v_src, kq, ks, vq, vs, cu_seqlens, kv_base, max_tokens, model_dtype=None, err=None):
+    """Rows [kv_base[b], kv_base[b] + cu_seqlens[b+1] - cu_seqlens[b]) of the model-dtype slabs k_src / v_src [B, nKV, T_src, d] -> the MXFP8 planes (codes kq / vq
+    uint8 [B, nKV, T_cap, d], scales ks / vs uint8 [B, nKV, T_cap, d/32]) at the same slots, bit-exact to mxfp8.quantize_mx8(rows, model_dtype).  Both vectors are read
+    on the device; max_tokens bounds the per-row count.  err: int32 [1], set to 1 by a NaN / Inf input (never cleared here)."""
+    _dev(k_src, v_src, kq, ks, vq, vs, cu_seqlens, kv_base)
+    B, nKV, T_src, d = k_src.shape
+    assert k_src.stride(3) == 1 and k_src.stride(2) == d and k_src.stride() == v_src.stride() and k_src.dtype == v_src.dtype
+    assert cu_seqlens.dtype == torch.int32 and kv_base.dtype == torch.int32 and cu_seqlens.numel() == B + 1
+    _kv8_planes(kq, ks, vq, vs, d)
+    md = k_src.dtype if model_dtype is None else model_dtype
+    _check(
+        lib().dl_kv_quantize_mx8(
+            _p(k_src), _p(v_src), k_src.stride(0), k_src.stride(1), T_src, _p(kq), _p(ks), _p(vq), _p(vs), kq.stride(0), kq.stride(1), kq.shape[2], _p(cu_seqlens), _p(kv_base),
+            int(max_tokens), B, nKV, d, dtype_code(k_src.dtype), dtype_code(md), _p(err), _stream(),
+        ),
+        "dl_kv_quantize_mx8",
+    )
+
+
+def attn_decode_rope_kv8(qkv, cos, sin, pos_base, kv_len, kq, ks, vq, vs, out, workspace, n_splits, n_heads, n_kv_heads, head_dim, keys_in_flight=128, chunk_keys=0):
+    """attn_decode_rope on the MXFP8 KV planes (see kv_quantize_mx8): RoPE, quantised append at slot kv_len[b], ragged attention over [dequantised old rows | exact
+    new row].  keys_in_flight: 128 (four waves) or 256 (eight waves)."""
+    _dev(qkv, cos, sin, pos_base, kv_len, kq, ks, vq, vs, out)
+    assert qkv.stride(1) == 1 and out.stride(1) == 1 and kv_len.dtype == torch.int32 and pos_base.dtype == torch.int32
+    _kv8_planes(kq, ks, vq, vs, head_dim)
+    B = qkv.shape[0]
+    _check(
+        lib().dl_attn_decode_rope_kv8(
+            _p(qkv), qkv.stride(0), _p(cos), _p(sin), cos.shape[0], _p(pos_base), _p(kv_len), _p(kq), _p(ks), _p(vq), _p(vs), kq.stride(0), kq.stride(1), kq.shape[2],
+            _p(out), out.stride(0), _p(workspace), int(n_splits), int(keys_in_flight), int(chunk_keys), B, n_heads, n_kv_heads, head_dim, dtype_code(qkv.dtype), _stream(),
+        ),
+        "dl_attn_decode_rope_kv8",
     )
     return out
 

@@ -119,6 +119,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self.decode_weight_format = None  # "mxfp8": see set_decode_weight_format()
         # MXFP8 only: decode steps of gemv_max_decode_batch < B <= this many rows stream the codes too (dl_gemm_mx8); None: the codes are used in the GEMV range only
         self.mx8_max_decode_batch = None
+        self.kv_cache_format = None  # "mxfp8": see set_kv_cache_format()
         self.eval()
 
     # ---- reference surface -----------------------------------------------------------------
@@ -233,6 +234,27 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._packed = False
         return self.finalize()  # (drops the decode state and its captured graphs: their keys and pointers belong to the old format)
 
+    # ---- MXFP8 KV cache ---------------------------------------------------------------------------
+    def set_kv_cache_format(self, fmt):
+        """Select the storage format of the KV cache this model allocates.  None (default): the model dtype.  "mxfp8": the kept keys (after RoPE) and values are
+        stored as MXFP8 codes along head_dim (cache.KVSlabCacheMX8: d + d/32 bytes per row, 0.516 of a 16-bit slab at d = 128; 0.26 of an fp32 one).
+
+        The prefill is unchanged arithmetic -- its attention reads K/V from the packed projection -- and appends through a one-layer model-dtype scratch slab that
+        dl_kv_quantize_mx8 moves into the layer's planes, so prefill logits are bit-identical to the format-off model's.  Decode steps run dl_attn_decode_rope_kv8:
+        the new token is attended exactly and stored quantised, older rows are read as their dequantised values (exact in the model dtype).  The fused batch-1
+        q|k|v + attention launch and the partial-sum attention launch are not used in this mode (the unfused branches run, as with MXFP8 weights).  Orthogonal to
+        set_decode_weight_format.  Not built in this mode (NotImplementedError): a multi-token chunk on a non-empty cache and generate(past_key_values=...).
+        use_cache=False is unaffected.  Changing the format drops the pooled cache and every graph captured on it."""
+        from .mxfp8 import check_kv_cache_format
+
+        check_kv_cache_format(fmt)
+        if fmt != self.kv_cache_format:
+            self.kv_cache_format = fmt
+            self._cache_pool = None
+            self._dstate = None
+            self._prefill_graphs = {}
+        return self
+
     def _quantize_decoder_weights(self):
         from .mxfp8 import dequantize_mx8
 
@@ -344,7 +366,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "tiles_o_proj": self.tiles_o_proj, "tiles_o_proj_min_decode_batch": self.tiles_o_proj_min_decode_batch,
             "clip_tiles_gemm": getattr(self.get_vision_tower(), "tiles_gemm", None), "clip_tiles_max_batch": getattr(self.get_vision_tower(), "tiles_max_batch", None),
             "clip_tiles_ksplit": [getattr(self.get_vision_tower(), "tiles_ksplit_out", None), getattr(self.get_vision_tower(), "tiles_ksplit_fc2", None)],
-            "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch,
+            "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch, "kv_cache_format": self.kv_cache_format,
             "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
@@ -378,7 +400,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             raise ValueError("You have to specify either input_ids or inputs_embeds")  # DML:1686-1695
         cache = past_key_values
         if cache is not None and not isinstance(cache, KVSlabCache):
-            cache = KVSlabCache.from_legacy_cache(cache, self.config.sparse_config["sparse_layer"], device=self.device)
+            cache = KVSlabCache.from_legacy_cache(cache, self.config.sparse_config["sparse_layer"], device=self.device, kv_format=self.kv_cache_format)
         decode = cache is not None and max(cache.full_len_host) > 0
         if decode:
             if input_ids is None:
@@ -540,6 +562,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if images is not None or kwargs.get("image_features") is not None:
             raise NotImplementedError("generate(past_key_values=...) continues a dialogue: the image belongs to the first call")
         cache = kwargs["past_key_values"]
+        if self.kv_cache_format is not None or getattr(cache, "kv_format", None) is not None:
+            raise NotImplementedError(f"generate(past_key_values=...) starts with a multi-token chunk on the cache, which is not built for the KV cache format "
+                                      f"{self.kv_cache_format or cache.kv_format!r} (the chunk-on-cache attention reads model-dtype rows)")
         if not isinstance(cache, KVSlabCache):
             cache = KVSlabCache.from_legacy_cache(cache, self.config.sparse_config["sparse_layer"], device=self.device)
         inputs = inputs.to(self.device)
@@ -678,7 +703,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
             key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
                    cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._eos, self._pad, min_new, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key(), self._sampled)  # (a knob toggled at run time must not replay a graph captured under the other setting)
+                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled)  # (a knob toggled at run time must not replay a graph captured under the other setting)
             ent = self._prefill_graphs.get(key)
             if ent is None:
                 # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream

@@ -129,6 +129,17 @@ def check_decode_weight_format(fmt, max_batch, gemv_max_decode_batch: int) -> No
         raise ValueError(f"max_batch={max_batch!r}: expected None or an int in [{gemv_max_decode_batch}, {GEMM_MAX_M}]")
 
 
+def check_kv_cache_format(fmt) -> None:
+    """Argument rule of set_kv_cache_format / load_pretrained_model: None (the model dtype) or "mxfp8".  Raises ValueError."""
+    if fmt not in (None, "mxfp8"):
+        raise ValueError(f"KV cache format {fmt!r}: expected None or 'mxfp8'")
+
+
+def kv_mx8_bytes(n_layers: int, batch: int, n_kv_heads: int, t_cap: int, head_dim: int) -> int:
+    """Bytes of an MXFP8 KV cache (cache.KVSlabCacheMX8): K and V, codes + one scale byte per 32 elements."""
+    return n_layers * 2 * batch * n_kv_heads * t_cap * (head_dim + head_dim // BLOCK)
+
+
 def gemm_mx8_slices(M: int, N: int, K: int, n_slices: int = 0) -> int:
     """The split-K factor dl_gemm_mx8 uses for a call (dl_gemm_mx8_slices); 0 for a shape it rejects.  n_slices 0 = automatic: 4 for the wide projections (at least
     1024 sixteen-neuron tiles), 8 otherwise; raised until one K slice of X (16 or 32 rows of the 16-bit dtype, rows padded by 8 elements) fits the LDS left beside the

@@ -261,6 +261,9 @@ class PrefillEngine:
         cos, sin = self._rope
         cu, cu_list, max_len, total = p["cu"], p["cu_list"], p["max_len"], (p["cu_list"][-1] if p["nocache"] else p["total"])
         zeros_b = p["zeros"]
+        # MXFP8 KV cache: dl_rope_kv_write appends into ONE layer's model-dtype scratch slab (reused by every layer), dl_kv_quantize_mx8 moves the rows into the layer's planes
+        kv8 = cache.kv_format == "mxfp8"
+        k_dst, v_dst = ([t] * L for t in cache.prefill_scratch()) if kv8 else (cache.k, cache.v)
         pos = None  # layers < SL: position = in-row index
         h = embeds.to(dt).contiguous()
         if h.shape[0] < total:  # sized for the width bucket (see _plan_prefill): the extra rows are zeros behind the last sequence
@@ -385,10 +388,12 @@ class PrefillEngine:
                 parts_q = ops.linear_packed(x, layer.wp_qkv, Nq, out=self._qkv_parts_ws(ks_q * ops.LP_MAX_ROWS * Nq), epilogue=ops.LP_PARTS, units_per_workgroup=nu_q, k_split=ks_q,
                                             x_packed_mk=(total, h.shape[1]))
                 qkv = qkv_buf
-                ops.rope_kv_write(qkv, cos, sin, cu, pos, zeros_b, zeros_b, cache.k[i], cache.v[i], nH, nKV, d, parts=parts_q)
+                ops.rope_kv_write(qkv, cos, sin, cu, pos, zeros_b, zeros_b, k_dst[i], v_dst[i], nH, nKV, d, parts=parts_q)
             else:
                 qkv = self._lp_linear(x, total, layer.wp_qkv, Nq, h.shape[1]) if use_lp else F.linear(x, layer.w_qkv)
-                ops.rope_kv_write(qkv, cos, sin, cu, pos, zeros_b, zeros_b, cache.k[i], cache.v[i], nH, nKV, d)
+                ops.rope_kv_write(qkv, cos, sin, cu, pos, zeros_b, zeros_b, k_dst[i], v_dst[i], nH, nKV, d)
+            if kv8:  # the scratch rows [0, cu[b+1] - cu[b]) of every sequence -> this layer's planes (the row counts are read on the device)
+                ops.kv_quantize_mx8(k_dst[i], v_dst[i], cache.k[i], cache.ks[i], cache.v[i], cache.vs[i], cu, zeros_b, max_len, model_dtype=dt)
             if attn_buf is None or attn_buf.shape[0] != total:
                 # one zero-filled buffer per row count, shared by the layers (the attention launch writes the rows of real sequences only: padding rows
                 # of a width bucket stay zero instead of holding whatever the allocator handed out -- ADVICE r4)
@@ -516,11 +521,13 @@ class PrefillEngine:
         cfg, sc = self.config, self.config.sparse_config
         p = self._plan_prefill(lens, indices)
         if cache is None:
-            cache = KVSlabCache(cfg.num_hidden_layers, sc["sparse_layer"], p["B"], cfg.num_key_value_heads, cfg.head_dim, max(lens) + reserve, self.dtype, self.device)
+            cache = self._new_cache(p["B"], max(lens) + reserve)
         elif max(cache.full_len_host) != 0:
             raise NotImplementedError("multi-token forward on a non-empty cache (new-instruct round, DML:2506-2521) is SURVEY 8f row N2")
         self._rope_tables(max(lens) + reserve)
         x = self._prefill_run(p, embeds, cache, indices, last_only)
+        if cache.kv_format == "mxfp8" and cache is not getattr(self, "_cache_pool", None):
+            cache.release_scratch()  # (a cache forward() hands to its caller: no captured graph holds the scratch's pointer -- those live on the pooled cache, which keeps it)
         self._prefill_host_update(p, cache, indices)
         if p["instruct_drop"]:
             n = p["lens2"][0] - p["instruct_drop"]
@@ -592,6 +599,9 @@ class PrefillEngine:
         instruct predictor, plain chunked prefill.  Every chunk token attends to the cache and causally to the chunk
         (CU:256-268 `get_cache`), then only the kept K/V rows stay in the slab (CU:165-241, without the zero padding)."""
         cfg, sc = self.config, self.config.sparse_config
+        if cache.kv_format is not None:
+            raise NotImplementedError(f"a multi-token chunk on a non-empty cache is not built for the KV cache format {cache.kv_format!r} "
+                                      "(dl_attn_prefill_cached and dl_kv_pack_rows read model-dtype rows)")
         if attention_mask is not None and not bool(attention_mask.bool().all()):
             raise NotImplementedError("padded chunks on a cache")
         dev, dt = self.device, self.dtype

@@ -173,6 +173,40 @@ int dl_attn_decode_rope_parts(const float* qkv_parts, int n_parts, int64_t part_
                               void* workspace, int n_splits, int chunk_keys, int call_tag, int B, int n_heads,
                               int n_kv_heads, int head_dim, int dtype, void* stream);
 
+/* ---- the MXFP8 KV cache (opt-in): the KV append (CU:109-268) and the decode attention (DML:1061-1122 with CU:256-268) on keys (after RoPE,
+ * DML:260-285) and values stored in the MXFP8 format below (dl_quantize_mx8's, dynamic_llava_amd/mxfp8.py) applied along head_dim.  Per layer, separate
+ * planes, no interleaving and no swizzle:
+ *   codes  uint8 [B, nKV, T_cap, d]     e4m3fn          scales uint8 [B, nKV, T_cap, d/32]   E8M0 code e + 127 of 32 consecutive elements of a row
+ * for K and for V: d + d/32 bytes per row.  plane strides are those of the CODE planes (bytes); a scale plane's are 1/32 of them (multiples of 32; code
+ * planes 16-byte aligned).  e = clamp(floor(log2(amax)) - 8, dl_mx8_e_min(model dtype), 127), codes by RNE saturated at +-448, an all-zero block gives
+ * e = 0, q = 0: every dequantised element q * 2^e is exactly representable in the model dtype.
+ *
+ * dl_kv_quantize_mx8: for batch row b the tokens j in [0, cu_seqlens[b+1] - cu_seqlens[b]) -- dl_rope_kv_write's addressing, both vectors read on the
+ * device -- are read at slot kv_base[b] + j of the model-dtype slabs k_src / v_src [B, nKV, src_T_cap, d] (strides in elements) and written, quantised,
+ * to the same slot of the planes.  max_tokens: host bound of the per-row token count (sizes the grid).  A slot at or past either capacity is dropped;
+ * slots outside the ranges are not touched.  Bit-exact to mxfp8.quantize_mx8(rows, model_dtype).  A NaN / Inf input sets *err_flag = 1 (may be NULL;
+ * never cleared here).  src_dtype: f32, f16 or bf16.  head_dim % 32 == 0.
+ *
+ * dl_attn_decode_rope_kv8: dl_attn_decode_rope on the planes, one launch (+ the merge launch when n_splits > 1): RoPE of q and of the new key with the
+ * same roundings; the rotated key row and the value row are quantised and appended at slot kv_len[b] (one writer per kv head; kv_len[b] >= T_cap writes
+ * nothing); ragged attention over keys [0, kv_len[b]].  n_splits / chunk_keys as dl_attn_decode_rope (the speculative form included); partials in
+ * dl_attn_decode_workspace_bytes' layout; ragged batches run longest row first.  keys_in_flight = 128 (four waves) or 256 (eight waves), counted at
+ * head_dim 128: a lane holds 16 codes, so a trip of the four-wave form requests 128 keys -- the bytes of dl_attn_decode_rope's 64.  head_dim 64 or 128,
+ * GQA, f32 / f16 / bf16.
+ * Numerics: slab keys [0, kv_len[b]) are read as K' = q * 2^e and V' = q * 2^e exactly -- codes converted at unit scale (v_cvt_scalef32_pk_f32_fp8), the
+ * dot product of a lane's 16 elements accumulated in fp32, the block's 2^e applied to that fp32 partial and, for V, to the fp32 softmax weight of the
+ * p * v term; no 16-bit subnormal is formed.  The NEW token is attended at model-dtype precision (its rotated key and its value are in registers) and
+ * stored quantised: the output is attention over [dequantised old rows | exact new row].  A masked or speculatively read slot may hold any bytes (NaN
+ * codes, scale 0xff): they never reach an accumulator.  fp32 online softmax, one rounding of the output (attn_decode_body.h). */
+int dl_kv_quantize_mx8(const void* k_src, const void* v_src, int64_t src_stride_b, int64_t src_stride_h, int src_T_cap, void* k_codes, void* k_scales,
+                       void* v_codes, void* v_scales, int64_t dst_stride_b, int64_t dst_stride_h, int dst_T_cap, const int32_t* cu_seqlens,
+                       const int32_t* kv_base, int max_tokens, int B, int n_kv_heads, int head_dim, int src_dtype, int model_dtype, int32_t* err_flag,
+                       void* stream);
+int dl_attn_decode_rope_kv8(const void* qkv, int64_t qkv_row_stride, const void* cos_tab, const void* sin_tab, int n_pos, const int32_t* pos_base,
+                            const int32_t* kv_len, void* k_codes, void* k_scales, void* v_codes, void* v_scales, int64_t plane_stride_b,
+                            int64_t plane_stride_h, int T_cap, void* out, int64_t out_row_stride, void* workspace, int n_splits, int keys_in_flight,
+                            int chunk_keys, int B, int n_heads, int n_kv_heads, int head_dim, int dtype, void* stream);
+
 /* ---- F2: top-k select, DML:1867 + 1898-1908.  score [B,n] in the model dtype (= log_softmax(...)[:,:,0]);
  * keep_idx [B,k] int64 ascending = the k largest scores; ties: the LOWER original index wins
  * (= stable descending sort; the reference's argsort is non-stable).  n <= 4096. */

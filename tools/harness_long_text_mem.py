@@ -8,7 +8,10 @@ past_key_values[0][-1][0].shape[-2]` and a record {total_token_length, kv_cache_
 to --result-file after every token.  This script drives the same loop through the same API surface; the dataset (LVIS instruct
 conversations) does not exist offline, so prompts / label ids are seeded random ids of the dataset's typical lengths.
 
-    python tools/harness_long_text_mem.py --gen-len 512 [--model 7b|13b|tiny] [--batch-size 1] [--result-file out.json]
+    python tools/harness_long_text_mem.py --gen-len 512 [--model 7b|13b|tiny] [--batch-size 1] [--result-file out.json] [--kv-format mxfp8]
+
+--kv-format mxfp8: the same walk with model.set_kv_cache_format("mxfp8") (kept keys / values stored as MXFP8 codes, 0.516 of the fp16 slab's bytes at head_dim 128).  The
+harness's own `pkv[0][-1][0].shape[-2]` then dequantises the last layer's rows on every step (one layer's worth of transient memory inside max_memory).
 """
 import argparse
 import json
@@ -77,6 +80,7 @@ def main(argv=None):
     ap.add_argument("--keep-rate", type=float, default=0.2)
     ap.add_argument("--layers", type=int, default=None)
     ap.add_argument("--result-file", default=None)
+    ap.add_argument("--kv-format", default=None, choices=["mxfp8"], help="KV cache storage format (default: the model dtype)")
     ap.add_argument("--no-operand-copies", action="store_true", help="build without the operand-order weight copies: `model memory` = the parameters, as in the reference")
     args = ap.parse_args(argv)
     knob_env = {"DL_PACKED_GEMM": "0", "DL_CLIP_TILES": "0"} if args.no_operand_copies else {}
@@ -103,6 +107,8 @@ def main(argv=None):
             os.environ.pop(k, None)
         else:
             os.environ[k] = v
+    if args.kv_format is not None:
+        model.set_kv_cache_format(args.kv_format)
     model_memory = torch.cuda.max_memory_allocated()
     #  memory the reference does not hold for the same checkpoint, reported beside BLTM:64's figure
     copies, param_bytes, live = model.operand_copy_bytes(), model.parameter_bytes(), torch.cuda.memory_allocated() - live_before_build
@@ -119,6 +125,8 @@ def main(argv=None):
     rec = run(model, cfg, input_ids, label_ids, images, model_memory, args.result_file)
     rec.update(model_memory=model_memory, operand_copy_bytes=copies, parameter_bytes=param_bytes, model_memory_without_operand_copies=live - copies["total"],
                operand_copies_built=not args.no_operand_copies)
+    if args.kv_format is not None:
+        rec.update(kv_format=args.kv_format)
     if args.result_file:
         with open(args.result_file, "w", encoding="utf-8") as f:
             json.dump(rec, f, ensure_ascii=False, indent=4)
