@@ -14,6 +14,7 @@
 #include <mutex>
 
 #include "gemv_dot.h"
+#include "gemv_prologue.h"
 #include "granule.h"
 #include "attn_decode_body.h"
 #include "tp_body.h"
@@ -32,7 +33,6 @@ __device__ long long g_gemv_stamps[8];
 #define DL_GSTAMP(i)
 #endif
 
-constexpr int kGemvThreads = 256;
 constexpr int kGemvR = 2;       // neurons per wave per pass
 constexpr int kGemvMaxB = 8;
 
@@ -82,113 +82,8 @@ __device__ __forceinline__ void gemv_body(const void* __restrict__ W_, int N, in
     }
   }
 
-  // ---- prologue: build x in LDS ----
-  if constexpr (MODE == 1) {  // ADDNORM
-    const S* h = reinterpret_cast<const S*>(h_);
-    S* h_out = reinterpret_cast<S*>(h_out_);
-    const S* dl_ = reinterpret_cast<const S*>(delta_);
-    const S* nw = reinterpret_cast<const S*>(nw_);
-    constexpr int MAXC = 4;  // 16-byte chunks per thread held in registers: K <= 256 * 4 * kVec (8192 for the 16-bit dtypes)
-    if (nvec <= kGemvThreads * MAXC) {
-      // every global load of the prologue (residual row, delta row, norm weight) is requested before anything is used: the
-      // prologue is then ONE L2 round trip + the reduction, instead of load -> reduce -> load
-      uint4 wr[MAXC];
-#pragma unroll
-      for (int c = 0; c < MAXC; ++c) {
-        const int v = tid + c * kGemvThreads;
-        if (v < nvec) wr[c] = *reinterpret_cast<const uint4*>(nw + v * V);
-      }
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        uint4 hr[MAXC], dr[MAXC];
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-          const int v = tid + c * kGemvThreads;
-          if (v < nvec) {
-            hr[c] = *reinterpret_cast<const uint4*>(h + (int64_t)b * K + v * V);
-            if (dl_) dr[c] = *reinterpret_cast<const uint4*>(dl_ + (int64_t)b * K + v * V);
-          }
-        }
-        float a[MAXC][V];
-        float ss = 0.f;
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-          const int v = tid + c * kGemvThreads;
-          if (v < nvec) {
-            unpack16<T>(hr[c], a[c]);
-            if (dl_) {
-              float d[V];
-              unpack16<T>(dr[c], d);
-#pragma unroll
-              for (int e = 0; e < V; ++e) a[c][e] = Elem<T>::round(a[c][e] + d[e]);
-              // updated residual stream: written once, to a DIFFERENT buffer (other workgroups are still reading h_in)
-              if (bid == 0) store16<T>(h_out + (int64_t)b * K + v * V, a[c]);
-            }
-#pragma unroll
-            for (int e = 0; e < V; ++e) ss += a[c][e] * a[c][e];
-          }
-        }
-        const float rstd = rsqrtf(block_sum<4>(ss, red) / (float)K + eps);
-#pragma unroll
-        for (int c = 0; c < MAXC; ++c) {
-          const int v = tid + c * kGemvThreads;
-          if (v < nvec) {
-            float w[V];
-            unpack16<T>(wr[c], w);
-#pragma unroll
-            for (int e = 0; e < V; ++e) a[c][e] = w[e] * Elem<T>::round(a[c][e] * rstd);
-            store16<T>(xs + b * K + v * V, a[c]);
-          }
-        }
-      }
-    } else {
-#pragma unroll
-      for (int b = 0; b < B; ++b) {
-        float ss = 0.f;
-        for (int v = tid; v < nvec; v += kGemvThreads) {
-          float a[V];
-          load16<T>(h + (int64_t)b * K + v * V, a);
-          if (dl_) {
-            float d[V];
-            load16<T>(dl_ + (int64_t)b * K + v * V, d);
-#pragma unroll
-            for (int e = 0; e < V; ++e) a[e] = Elem<T>::round(a[e] + d[e]);
-            if (bid == 0) store16<T>(h_out + (int64_t)b * K + v * V, a);
-          }
-#pragma unroll
-          for (int e = 0; e < V; ++e) ss += a[e] * a[e];
-          store16<T>(xs + b * K + v * V, a);
-        }
-        const float rstd = rsqrtf(block_sum<4>(ss, red) / (float)K + eps);
-        for (int v = tid; v < nvec; v += kGemvThreads) {
-          float a[V], w[V];
-          load16<T>(xs + b * K + v * V, a);
-          load16<T>(nw + v * V, w);
-#pragma unroll
-          for (int e = 0; e < V; ++e) a[e] = w[e] * Elem<T>::round(a[e] * rstd);
-          store16<T>(xs + b * K + v * V, a);
-        }
-      }
-    }
-  } else if constexpr (MODE == 2) {  // SILUMUL: x_ = gate_up [B, 2K]
-    const S* gu = reinterpret_cast<const S*>(x_);
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-      for (int v = tid; v < nvec; v += kGemvThreads) {
-        float g[V], u[V];
-        load16<T>(gu + (int64_t)b * x_rs + v * V, g);
-        load16<T>(gu + (int64_t)b * x_rs + K + v * V, u);
-#pragma unroll
-        for (int e = 0; e < V; ++e) g[e] = Elem<T>::round(g[e] / (1.0f + expf(-g[e]))) * u[e];
-        store16<T>(xs + b * K + v * V, g);
-      }
-  } else {
-    const S* x = reinterpret_cast<const S*>(x_);
-#pragma unroll
-    for (int b = 0; b < B; ++b)
-      for (int v = tid; v < nvec; v += kGemvThreads)
-        *reinterpret_cast<uint4*>(xs + b * K + v * V) = *reinterpret_cast<const uint4*>(x + (int64_t)b * x_rs + v * V);
-  }
+  // ---- prologue: build x in LDS (gemv_prologue.h) ----
+  gemv_build_x<T, B, MODE>(xs, red, K, x_, x_rs, h_, h_out_, delta_, nw_, eps, bid);
   __syncthreads();
   DL_GSTAMP(1);  // x is in LDS
 
@@ -256,8 +151,7 @@ __device__ __forceinline__ void gemv_body(const void* __restrict__ W_, int N, in
         if (n0 < n_out) {
 #pragma unroll
           for (int b = 0; b < B; ++b) {
-            const float g = Elem<T>::round(acc[0][b]), u = Elem<T>::round(acc[1][b]);
-            store1<T>(y_, (int64_t)b * y_rs + n0, Elem<T>::round(g / (1.0f + expf(-g))) * u);
+            store1<T>(y_, (int64_t)b * y_rs + n0, gemv_silu_pair<T>(acc[0][b], acc[1][b]));
           }
         }
       } else {

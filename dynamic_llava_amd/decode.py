@@ -146,9 +146,13 @@ class DecodeScheduler:
         # MXFP8 decoder weights (set_decode_weight_format): the four projections stream (q, scale) on dl_gemv_mx8; the two fused model-dtype launches
         # (dl_gemv_qkv_attn, dl_gemv_gu_tp) are not used -- the unfused sequence runs instead (stand-alone attention, the predictor's decide)
         mx8 = self.decode_weight_format == "mxfp8"
+        # batch 1, model-dtype format: the matrices that have a 12-bit packed copy (model._pack_decode_weights) stream it on dl_gemv_pk -- same bits out
+        pack = self.decode_weight_pack and st.B == 1 and self.decode_weight_format is None
+        no_pk = {"o": None, "gu": None, "down": None}
         for i, layer in enumerate(self.model.layers):
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
+            pk = (getattr(layer, "pk", None) or no_pk) if pack else no_pk
             if mx8:
                 self._decode_layer_mx8(st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp)
                 if delta is not None:
@@ -188,17 +192,28 @@ class DecodeScheduler:
             # only when the row is long enough to need more than one workgroup per head)
             if not fused_attn:
                 self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
-            ops.gemv(layer.self_attn.o_proj.weight, st.o, x=st.attn)
-            if fused_tp:
+            if pk["o"] is not None:
+                ops.gemv_pk(pk["o"], st.o, x=st.attn)
+            else:
+                ops.gemv(layer.self_attn.o_proj.weight, st.o, x=st.attn)
+            if fused_tp:  # (this one layer keeps the model-dtype weights: the launch carries the predictor)
                 tp = self.model.output_text_score_predictor
                 ops.gemv_gu_tp(layer.w_gu, st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
                                st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
+            elif pk["gu"] is not None:
+                ops.gemv_pk(pk["gu"], st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps, grid_cap=self.gu_grid_cap)
             else:
                 ops.gemv(layer.w_gu, st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps, grid_cap=self.gu_grid_cap)
             h_cur, h_alt = h_alt, h_cur
-            ops.gemv(layer.mlp.down_proj.weight, st.dn, x=st.gu)
+            if pk["down"] is not None:
+                ops.gemv_pk(pk["down"], st.dn, x=st.gu)
+            else:
+                ops.gemv(layer.mlp.down_proj.weight, st.dn, x=st.gu)
             delta = st.dn
-        ops.gemv(self.lm_head.weight, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
+        if pack and getattr(self, "_pk_lm_head", None) is not None:
+            ops.gemv_pk(self._pk_lm_head, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
+        else:
+            ops.gemv(self.lm_head.weight, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
         if use_tp and self.tp_side_stream:
             torch.cuda.current_stream().wait_stream(st.tp_stream)  # join before anything reads st.decision
 
@@ -426,7 +441,7 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
+               self.decode_weight_pack, self.decode_weight_pack_plain, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
                self._kv_format_key(cache), bool(getattr(self, "_sampled", False)))  # (sampled or greedy: which bookkeeping kernel was captured; the sampling parameters are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):

@@ -101,6 +101,7 @@ SIGNATURES = {
     "dl_text_predictor_workspace_bytes": (c_int64, [c_int, c_int]),
     "dl_gemv_max_batch": (c_int, [c_int, c_int]),
     "dl_gemv": (c_int, [c_int, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
+    "dl_gemv_pk": (c_int, [c_int, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int, c_int, c_int, c_void_p]),
     "dl_mx8_e_min": (c_int, [c_int]),
     "dl_quantize_mx8": (c_int, [c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_gemv_mx8": (c_int, [c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_int64, c_int, c_int, c_int, c_void_p]),
@@ -637,6 +638,30 @@ def gemv(w, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_
     _check(
         lib().dl_gemv(mode, _p(w), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(w.dtype), int(grid_cap), _stream()),
         "dl_gemv",
+    )
+    return y
+
+
+def gemv_pk_ok(mode, K, dtype):
+    """Shapes dl_gemv_pk takes (batch 1): a matrix outside them keeps its model-dtype launch."""
+    if dtype != torch.bfloat16 or K % 64 != 0:
+        return False
+    return (K % 1024 == 0 and K <= 8192) if (mode & 3) == GEMV_ADDNORM else ((mode & 3) == GEMV_PLAIN and K <= 16384)
+
+
+def gemv_pk(p, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_w=None, eps=0.0, grid_cap=0):
+    """gemv() at batch 1 on a losslessly packed bf16 weight (p: bf16pack.PackedBf16 of w [N,K]): bit-identical to gemv(w, ...), 0.75-0.8 of the bytes."""
+    _dev(p.data, p.hdr, p.pool, y, x, h_in, h_out, delta, norm_w)
+    assert p.data.dtype == torch.uint8 and p.pool.dtype == torch.uint8 and p.hdr.dtype == torch.int32 and p.data.is_contiguous() and p.hdr.is_contiguous() and p.pool.is_contiguous()
+    assert y.dtype == torch.bfloat16 and y.shape[0] == 1 and y.stride(1) == 1
+    if (mode & 3) == GEMV_ADDNORM:
+        assert h_in.is_contiguous() and h_in.shape == (1, p.K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
+    else:
+        assert x.stride(1) == 1 and x.shape[0] == 1 and x.shape[1] >= p.K
+    _check(
+        lib().dl_gemv_pk(mode, _p(p.data), p.data.numel(), _p(p.hdr), p.hdr.shape[0], _p(p.pool), p.pool.numel() // 1024, int(p.hb), p.N, p.K, _p(x), _p(h_in), _p(h_out),
+                         _p(delta), _p(norm_w), eps, _p(y), 1, dtype_code(y.dtype), int(grid_cap), _stream()),
+        "dl_gemv_pk",
     )
     return y
 

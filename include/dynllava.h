@@ -299,6 +299,17 @@ int dl_gemv(int mode, const void* W, int N, int K, const void* x, int64_t x_row_
             const void* delta, const void* norm_w, float eps, void* y, int64_t y_row_stride, int B, int dtype, int grid_cap,
             void* stream);
 
+/* ---- dl_gemv on LOSSLESS 12-bit packed bf16 weights (dynamic_llava_amd/bf16pack.py defines the format: low bytes verbatim, sign + 3-bit exponent-window
+ * offset per weight, spans with an out-of-window element also raw in a pool).  Batch 1, bf16; modes DL_GEMV_PLAIN (K <= 16384), DL_GEMV_ADDNORM and
+ * DL_GEMV_ADDNORM | DL_GEMV_OUT_SILU_PAIR (K % 1024 == 0, K <= 8192).  K % 64 == 0.  x / h_in / y as dl_gemv's with one row.  The kernel rebuilds the bf16
+ * words in registers and runs dl_gemv's arithmetic in dl_gemv's order: y (and h_out) are bit-identical to dl_gemv on the unpacked weights.
+ * data: N rows of K * 3 / 2 bytes (data_bytes is checked), hdr: hdr_rows >= N x {uint32 span mask, uint32 first pool span}, pool: pool_spans >= 1 spans of
+ * 1024 bytes; hb: the matrix's window start, 0..120.  data / pool 16-byte aligned.  Sizes are checked here (DL_ERR_ARG, nothing is launched); the pool index
+ * a header leads to is clamped to the pool by the kernel, so no header content makes it read outside the three buffers. */
+int dl_gemv_pk(int mode, const void* data, int64_t data_bytes, const void* hdr, int64_t hdr_rows, const void* pool, int64_t pool_spans, int hb, int N, int K,
+               const void* x, const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y, int B, int dtype, int grid_cap,
+               void* stream);
+
 /* ---- MXFP8 decoder weights (OCP Microscaling v1.0 MXFP8 along K; dynamic_llava_amd/mxfp8.py is the host reference) ----
  * q: uint8 [N, K] row-major, OCP FP8 E4M3 "e4m3fn" codes (not the fnuz encoding); scale: uint8 [N, K/32] row-major, the E8M0 code e + 127 of
  * the block of 32 consecutive K elements q[n, 32j .. 32j+31].  W' = q * 2^e.  No interleaving or swizzle.  K % 32 == 0.
