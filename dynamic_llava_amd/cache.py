@@ -227,6 +227,18 @@ class KVSlabCache:
         self.t_cap = new_cap
         return True
 
+    def detached_copy(self):
+        """An independent cache with the same contents (its own storage and length vectors): what score() hands to the caller, so that the pooled slab --
+        and every captured graph that holds pointers into it -- stays with the model."""
+        import copy
+
+        c = copy.copy(self)
+        c._allocate(self.t_cap, keep_rows=self.t_cap)  # (reads this cache's storage, binds new storage to the copy)
+        c.lens = self.lens.clone()
+        c.full_len_host = list(self.full_len_host)
+        c._sch = copy.deepcopy(self._sch)
+        return c
+
     # ---- reference-compatible surface ----
     def __len__(self):
         return self.n_layers

@@ -17,22 +17,11 @@
 // per bin indexed by lane so that the few bins a narrow logit distribution hits are not one serialised address.  The draw is one 64-bit block scan of
 // the per-thread kept masses (index order = thread order) and a walk over one thread's registers.  Every loop has a fixed trip count; no workspace.
 #include "dl_common.h"
+#include "fixed_mass.h"
 
 namespace dl {
 
-constexpr int kSampleMassBits = 40;  // sampling.py S_BITS
-constexpr int kSampleMaxV = 65536;   // V * 2^40 < 2^63
 constexpr int kHistCopies = 16;
-
-// floor(w * 2^40) for 0 <= w <= 1 (exact: a shift of the significand)
-__device__ __forceinline__ uint64_t sample_mass(float w) {
-  const uint32_t u = __float_as_uint(w);
-  const int e = (int)((u >> 23) & 255u);
-  if (e == 0 || e > 127 || (u >> 31)) return 0;  // zero / denormal (< 2^-126) / negative / not a weight (> 1, inf, NaN)
-  const uint64_t mant = (uint64_t)((u & 0x7fffffu) | 0x800000u);
-  const int sh = e - 127 - 23 + kSampleMassBits;
-  return sh >= 0 ? (mant << sh) : (sh > -24 ? (mant >> (-sh)) : 0ull);
-}
 
 // order-preserving keys; key 0 is reserved for entries that take no part (banned, past the end of the row)
 __device__ __forceinline__ uint32_t sample_key16(uint32_t u) {

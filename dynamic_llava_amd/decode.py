@@ -78,6 +78,11 @@ class _DecodeState:
         # dl_decode_sample's parameter block (temperature, top-k, top-p, seed, row base): device memory the captured launches read, rewritten by
         # generate() before the first launch of a sampled request -- one graph serves every setting
         self.sample_params = ops.sample_params_block(device)
+        # dl_decode_score's label sequence and outputs (score()): refilled by the host before the first launch of a scoring request, outside any graph -- the
+        # pointers are stable, so one captured graph serves every label sequence.  Slot j belongs to step j, like out_ids
+        self.labels = torch.full(self.out_ids.shape, -100, dtype=torch.int64, device=device)
+        self.nll = torch.zeros(self.out_ids.shape, dtype=torch.float32, device=device)
+        self.top1 = torch.full(self.out_ids.shape, -1, dtype=torch.int64, device=device)
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
         self.tp_gran = ops.gemv_gu_tp_workspace(tpm.d_model, device) if (B == 1 and tpm is not None and dtype in (torch.bfloat16, torch.float16) and H <= 5120 and H % 8 == 0 and tpm.d_model % 32 == 0) else None
@@ -121,7 +126,10 @@ class DecodeScheduler:
         if advance:
             sc = self.config.sparse_config
             use_tp = bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and sc["sparse_layer"] < self.config.num_hidden_layers
-            if getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
+            if getattr(self, "_forced", False):  # score(): the same bookkeeping around the label, scored
+                ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, cache.len_full, cache.len_sparse,
+                                 st.decision if use_tp else None)
+            elif getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
                 ops.decode_sample(
                     st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
                     st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
@@ -442,7 +450,7 @@ class DecodeScheduler:
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
                self.decode_weight_pack, self.decode_weight_pack_plain, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
-               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)))  # (sampled or greedy: which bookkeeping kernel was captured; the sampling parameters are device data, not part of the key)
+               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured; the sampling parameters and the labels are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)
@@ -471,7 +479,9 @@ class DecodeScheduler:
             torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
         self._prefill_logits_buf.copy_(st.logits)
         # first token: argmax only (the prompt's KV lengths are already in place); EOS is banned while step < min_new (HF semantics)
-        if getattr(self, "_sampled", False):  # token 0 is drawn with step = 0
+        if getattr(self, "_forced", False):  # label 0 is scored on the prompt's last logits
+            ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, None, None, None)
+        elif getattr(self, "_sampled", False):  # token 0 is drawn with step = 0
             ops.decode_sample(st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)
         else:
             ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)

@@ -158,6 +158,10 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p],
     ),
+    "dl_decode_score": (
+        c_int,
+        [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
+    ),
 }
 
 _lib = None
@@ -866,6 +870,32 @@ def decode_sample(logits, next_ids, params, out_ids=None, step=None, finished=No
             _p(kv_len_full), _p(kv_len_sparse), _p(decision), int(min_new_tokens), _p(params), _p(kept_mask), _stream(),
         ),
         "dl_decode_sample",
+    )
+    return next_ids
+
+
+def decode_score(logits, next_ids, labels, nll, top1=None, out_ids=None, step=None, finished=None, pad_id=0, kv_len_full=None, kv_len_sparse=None, decision=None):
+    """dl_decode_advance's bookkeeping around a LABEL, scored (include/dynllava.h, scoring.py).  labels: int64 [B, label_cap] DEVICE tensor (an entry outside
+    [0, V) means "no label": the row is exhausted); nll: fp32 [B, label_cap]; top1: optional int64 [B, label_cap].  Slot step[b] of a live row is written."""
+    _dev(logits, next_ids, labels, nll, top1)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
+    B, V = logits.shape
+    label_cap = 0
+    if labels is not None:  # (None reaches the library, which refuses it)
+        assert labels.dtype == torch.int64 and labels.dim() == 2 and labels.shape[0] == B and labels.is_contiguous()
+        label_cap = labels.shape[1]
+    if nll is not None:
+        assert nll.dtype == torch.float32 and nll.is_contiguous() and (labels is None or nll.shape == labels.shape)
+        label_cap = label_cap or nll.shape[1]
+    if top1 is not None:
+        assert top1.dtype == torch.int64 and top1.is_contiguous() and top1.shape == (B, label_cap)
+    out_cap = out_ids.shape[1] if out_ids is not None else 0
+    _check(
+        lib().dl_decode_score(
+            _p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(labels), int(label_cap), _p(nll), _p(top1), _p(next_ids), _p(out_ids), out_cap, _p(step), _p(finished),
+            int(pad_id), _p(kv_len_full), _p(kv_len_sparse), _p(decision), _stream(),
+        ),
+        "dl_decode_score",
     )
     return next_ids
 

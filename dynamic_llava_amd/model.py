@@ -33,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import sampling
+from . import sampling, scoring
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -428,7 +428,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         bit-identical to generate()'s), and calling check_device_errors() at a convenient sync point is the caller's job."""
         self._check_ready(weights=past_key_values is None)  # (the ~0.1 ms weight-fingerprint check runs where a sequence starts, not on every decode step of a forward() loop)
         if labels is not None:
-            raise NotImplementedError("labels / loss are training-side (DML:2713-2800), out of scope")
+            raise NotImplementedError("labels / loss are training-side (DML:2713-2800), out of scope; score() gives the teacher-forced NLL of a labelled continuation")
         if output_attentions or output_hidden_states:
             raise NotImplementedError("output_attentions / output_hidden_states are not produced by the fused path")
         if use_cache is False:
@@ -648,6 +648,36 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         return seq
 
     @torch.no_grad()
+    def score(self, input_ids, labels, images=None, image_sizes=None, *, attention_mask=None, image_features=None, sync_every=None, output_logits=False):
+        """Teacher-forced negative log-likelihood of a labelled continuation, on the device inside generate()'s captured graphs: the reference's
+        generation-time perplexity driver (llava/dynamic_eval/model_lvis_for_ppl.py:136-191 -- forward, take the last position's logits, record the
+        label, feed the label) with dl_decode_score where greedy decoding has dl_decode_advance (the rule is scoring.py).
+        input_ids [B, W]: the prompt exactly as generate() takes it.  labels: int64 [B, T], T >= 1; -100 marks "no label" and is allowed only as the
+        tail of a row (column 0 holds a label in every row); anything else outside [0, V), or a row count other than input_ids', raises ValueError
+        before any launch.  Step j scores labels[:, j] on the logits after prompt + labels[:, :j], then feeds labels[:, j]: one prefill + T - 1
+        decode steps (the last label of the longest row is scored and never run through the decoder, as in the reference loop).
+        -> dict: nll fp32 [B, T] (0 where there is no label), n_labels int64 [B], ppl fp32 [B] = exp(sum nll / n_labels), top1 int64 [B, T] (the greedy
+        token of every scored step, -1 where there is no label), past_key_values (the caller's own: an independent copy of the cache, so the pooled slab and
+        the graphs captured on it serve the next call of the same shape);
+        output_logits=True adds logits: a tuple of fp32 [B, V], one per step (the step-by-step route of generate(output_logits=True), for tests)."""
+        if not torch.is_tensor(input_ids) or input_ids.dim() != 2:
+            raise ValueError("input_ids must be a tensor [B, W]")
+        if self.config.vocab_size > sampling.MAX_VOCAB:
+            raise ValueError(f"score() takes vocabularies of up to {sampling.MAX_VOCAB} entries (dl_decode_score's 64-bit fixed-point masses)")
+        n_labels = scoring.validate_labels(labels, input_ids.shape[0], self.config.vocab_size)
+        kw = dict(max_new_tokens=int(labels.shape[1]), min_new_tokens=0, eos_token_id=None, return_dict_in_generate=True, output_logits=bool(output_logits),
+                  attention_mask=attention_mask, image_features=image_features, _score_labels=labels.detach().to("cpu").contiguous())
+        if sync_every is not None:
+            kw["sync_every"] = sync_every
+        res = self.generate(input_ids, images=images, image_sizes=image_sizes, **kw)
+        nll = res["nll"]
+        n_dev = n_labels.to(nll.device)
+        out = {"nll": nll, "n_labels": n_dev, "ppl": torch.exp(nll.sum(dim=1) / n_dev.to(torch.float32)), "top1": res["top1"], "past_key_values": res["past_key_values"]}
+        if output_logits:
+            out["logits"] = res["logits"]
+        return out
+
+    @torch.no_grad()
     def generate(self, inputs=None, images=None, image_sizes=None, **kwargs):
         """dynamic_llava_llama.py:117-152: greedy decoding; returns the NEW tokens only [B, T_new] (HF behaviour when
         generation is driven by inputs_embeds).  Supported kwargs: max_new_tokens / max_length, min_new_tokens (EOS banned from
@@ -728,6 +758,13 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._sampled = sampled is not None  # which bookkeeping kernel _first_token / the decode steps launch (and capture)
         if sampled is not None:
             st.sample_params.copy_(ops.sample_params_words(*sampled))
+        forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
+        self._forced = forced is not None  # dl_decode_score in the place of dl_decode_advance: score the label, feed the label
+        if forced is not None:
+            st.labels.fill_(scoring.IGNORE)
+            st.labels[:, : forced.shape[1]].copy_(forced)
+            st.nll.zero_()
+            st.top1.fill_(-1)
         if getattr(self, "_prefill_logits_buf", None) is None or self._prefill_logits_buf.shape != st.logits.shape:
             self._prefill_logits_buf = torch.empty(st.logits.shape, dtype=torch.float32, device=self.device)
         vp = getattr(self.model, "image_score_predictor", None)
@@ -740,7 +777,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
             key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
                    cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._eos, self._pad, min_new, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled)  # (a knob toggled at run time must not replay a graph captured under the other setting)
+                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled, self._forced)  # (a knob toggled at run time must not replay a graph captured under the other setting)
             ent = self._prefill_graphs.get(key)
             if ent is None:
                 # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
@@ -854,7 +891,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 st.obs_ev[slot].synchronize()
                 row = st.obs_host[slot]
                 cache.sched_observe(at, int(row[B : 2 * B].max()))
-                if eos_ids and int(row[2 * B :].min()) != 0:
+                if (eos_ids or self._forced) and int(row[2 * B :].min()) != 0:  # (score(): finished = labels exhausted)
                     all_done = True
             if all_done:
                 break
@@ -871,7 +908,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             if produced < max_new:
                 slot = chunks % 4
                 st.obs_host[slot, : 2 * B].copy_(cache.lens.view(-1), non_blocking=True)
-                if eos_ids:
+                if eos_ids or self._forced:
                     st.obs_host[slot, 2 * B :].copy_(st.finished, non_blocking=True)
                 st.obs_ev[slot].record()
                 pending.append((slot, produced))
@@ -904,6 +941,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             tm["ev"][2].record()
             tm["new_tokens"] = int(out.shape[1])
             self.last_timing = tm
+        if forced is not None:
+            # score(): the caller gets an independent COPY of the cache -- a perplexity run is many calls of one shape, and detaching the pooled slab (as below)
+            # would drop the captured graphs after every one of them
+            return {"sequences": out, "past_key_values": cache.detached_copy(), "logits": tuple(raw_logits), "nll": st.nll[:, : forced.shape[1]].clone(),
+                    "top1": st.top1[:, : forced.shape[1]].clone()}
         if want_dict:
             # the caller keeps this cache (the reference returns an independent one per call): detach it from the pool, the next
             # generate() allocates a fresh slab instead of overwriting this one

@@ -422,6 +422,28 @@ int dl_decode_sample(const void* logits, int logits_dtype, int64_t logits_row_st
                      int eos_id, int eos_id2, int eos_id3, int pad_id, int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision,
                      int min_new_tokens, const dl_sample_params* params, uint8_t* kept_mask, void* stream);
 
+/* ---- scored decode step (teacher forcing): dl_decode_advance with the argmax replaced by "score the label, feed the label" -- the step of the
+ * reference's generation-time perplexity driver (llava/dynamic_eval/model_lvis_for_ppl.py:136-191); the same bookkeeping, statement for statement
+ * (out_ids / step / kv_len_*; those pointers may be NULL as they may there).  There is no EOS set: the label sequence ends a row.
+ * With s = step[b] (0 when step is NULL): if the row is not finished, s < label_cap and 0 <= labels[b, s] < V, then nll[b, s] and top1[b, s] are
+ * written and the token is labels[b, s]; otherwise the row's labels are exhausted: finished[b] = 1, the token is pad_id, and nll / top1 at that slot
+ * are NOT written.  A label outside [0, V) is never used as an index.
+ * The rule, per row (dynamic_llava_amd/scoring.py states it in full and is what the kernel is tested against):
+ *   1. x_v = float32(logit_v); m = max_v x_v; top1 = the lowest index attaining m (dl_decode_advance's tie rule).
+ *   2. w_v = expf(x_v - m), the subtraction in fp32.
+ *   3. mass_v = floor(w_v * 2^40) as a 64-bit integer (zero, denormal and NaN weights give 0: dl_decode_sample's masses).
+ *   4. M = sum_v mass_v: an integer sum, exact and order-independent -- the same bits in every run, on the 16-byte-load and the scalar-load
+ *      route, and for a row alone or inside a batch.  2^40 <= M < 2^57.
+ *   5. lse = logf(float32(M) * 2^-40): u64 -> fp32 rounds to nearest even, the scaling is exact.
+ *   6. d = m - x_label; nll = d + lse: two fp32 operations, in this order.
+ * A logit of -inf has mass 0; a label whose logit is -inf scores +inf.  NaN logits are not supported (as in the greedy argmax).
+ * logits: bf16 / fp16 / fp32, V <= 65536 (DL_ERR_ARG beyond).  labels: int64 [B, label_cap]; nll: float [B, label_cap]; top1: int64 [B, label_cap]
+ * or NULL.  No workspace, no global atomics, never synchronises: capturable. */
+int dl_decode_score(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
+                    const int64_t* labels, int label_cap, float* nll, int64_t* top1,
+                    int64_t* next_ids, int64_t* out_ids, int out_cap, int32_t* step, int32_t* finished, int pad_id,
+                    int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision, void* stream);
+
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
  * operand registers).  bf16 / f16, fp32 accumulate, one rounding.  K % 256 == 0, N % 4 == 0; ldx / ldy: row strides (elements).
