@@ -12,11 +12,13 @@
 // coalesced, non-temporal: every weight byte is used exactly once per step).  fp32 accumulate, 6-step wave
 // reduction, one rounding to the model dtype -- the same contract as the GEMM it replaces.
 #include <mutex>
+#include <type_traits>
 
 #include "gemv_dot.h"
 #include "gemv_prologue.h"
 #include "granule.h"
 #include "attn_decode_body.h"
+#include "gemv_pk.h"
 #include "tp_body.h"
 #include "../../include/dynllava.h"
 
@@ -372,15 +374,30 @@ struct QkvAttnArgs {
   int n_splits, chunk_keys;  // attention workgroups per head, keys per workgroup (the last one takes the rest)
 };
 
+// dl_gemv_qkv_attn_pk: the same launch with the projection rows read as 12-bit packed bf16 (gemv_pk.h) -- the attention half does not know
+struct QkvAttnPkArgs : QkvAttnArgs {
+  PkMat m;
+};
+// rows per wave per pass of the packed projection (4 pairs of each in flight).  TWO: 192 bytes per lane in flight against the bf16 body's 128, and a pass of
+// the grid covers ~8 x 992 rows, so the q rows are the first 52 % of the first pass = the first third of the stream.  One row (96 bytes in flight, q = the
+// whole first pass) measured slower at every length: at T = 60 / 200 / 250 / 695 it saved -0.26 / 0.71 / 0.45 / 0.07 us against the bf16 launch where two
+// rows save 0.26 / 1.05 / 0.91 / 1.25 us (tools/bench_qkv_attn_pk.py, profiles/r08_qkv_attn_pk_per_launch.txt).  Same register count either way (115 / 128:
+// the attention path sets it).
+#ifndef DL_QA_PK_R
+#define DL_QA_PK_R 2
+#endif
+constexpr int kQaPkR = DL_QA_PK_R, kQaPkPre = DL_QA_PK_R == 1 ? 4 : 2;
+
 constexpr int kQaMaxSplits = 4;
 
 // four workgroups per CU or the grid (projection + attention workgroups) is not resident at once: hold the kernel to 128 VGPRs
 // MULTI: several attention workgroups per head (run-time n_splits).  Two instantiations because the general form needs ~20 VGPRs more than the
 // one-workgroup-per-head form (126), and the grid is only resident at once with four workgroups per CU = 128 VGPRs: the general form is held to
 // that by the attribute (a few dwords of spill in the attention path, measured faster than three workgroups per CU by far).
-template <typename T, int D, bool MULTI>
-__global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemv_qkv_attn_kernel(QkvAttnArgs a_) {
-  QkvAttnArgs a = a_;
+// PK: the projection workgroups run gemv_pk_body on a.m instead of gemv_body on a.W (bf16 only); nothing else differs.
+template <typename T, int D, bool MULTI, bool PK = false>
+__global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemv_qkv_attn_kernel(std::conditional_t<PK, QkvAttnPkArgs, QkvAttnArgs> a_) {
+  std::conditional_t<PK, QkvAttnPkArgs, QkvAttnArgs> a = a_;
   if constexpr (!MULTI) a.n_splits = 1;
   using S = typename Elem<T>::storage;
   const uint32_t tag = ((((uint32_t)a.pos_base[0] & 0x7fffffu) << 8) | ((uint32_t)a.call_tag & 0xffu)) + 1u;
@@ -389,7 +406,8 @@ __global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(4,
   const int n_gemv = (int)gridDim.x - a.n_heads * a.n_splits;
   DL_QSTAMP(0);
   if ((int)blockIdx.x < n_gemv) {
-    gemv_body<T, 1, 1, false, kQaR, kQaU>(a.W, a.N, a.K, nullptr, 0, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, a.N, (int)blockIdx.x, n_gemv, a.gran, tag);
+    if constexpr (PK) gemv_pk_body<false, kQaPkR, 4, kQaPkPre>(a.m, a.N, a.K, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, (int)blockIdx.x, n_gemv, a.gran, tag);
+    else gemv_body<T, 1, 1, false, kQaR, kQaU>(a.W, a.N, a.K, nullptr, 0, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, a.N, (int)blockIdx.x, n_gemv, a.gran, tag);
     DL_QSTAMP(1);
     return;
   }
@@ -540,14 +558,20 @@ struct GuTpArgs {
   int D, call_tag;
 };
 
+struct GuTpPkArgs : GuTpArgs {
+  PkMat m;
+};
+
 // MAXC: 16-byte chunks per lane of a stage-1 weight row held in registers (8: H <= 4096, 10: H <= 5120).  With 8 and two passes of stage 2b
 // in flight the kernel needs 121 VGPRs -- four workgroups per CU like the plain projection (135 / 237 VGPRs held three / two).
-template <typename T, int MAXC>
-__global__ __launch_bounds__(kGemvThreads) void gemv_gu_tp_kernel(GuTpArgs a) {
+// PK: the projection workgroups run the packed PAIR body (gemv_pk.hip's gate|up schedule) on a.m instead of gemv_body on a.W (bf16 only).
+template <typename T, int MAXC, bool PK = false>
+__global__ __launch_bounds__(kGemvThreads) void gemv_gu_tp_kernel(std::conditional_t<PK, GuTpPkArgs, GuTpArgs> a) {
   const int D = a.D, n1 = (D + 7) / 8, n2 = (D / 2 + 7) / 8, side = n1 + n2 + 1;
   const int bid = blockIdx.x, tid = threadIdx.x;
   if (bid >= side) {
-    gemv_body<T, 1, 1, true, 2, 4>(a.W, a.N, a.K, nullptr, 0, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, a.N / 2, bid - side, (int)gridDim.x - side, nullptr, 0u);
+    if constexpr (PK) gemv_pk_body<true, 2, 4, 2>(a.m, a.N, a.K, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, bid - side, (int)gridDim.x - side, nullptr, 0u);
+    else gemv_body<T, 1, 1, true, 2, 4>(a.W, a.N, a.K, nullptr, 0, a.h, a.h_out, a.delta, a.nw, a.eps, a.y, a.N / 2, bid - side, (int)gridDim.x - side, nullptr, 0u);
     return;
   }
   extern __shared__ __attribute__((aligned(16))) float gt_dyn[];  // >= max(H, 2 D) floats (host)
@@ -656,6 +680,36 @@ extern "C" int dl_gemv_gu_tp(const void* W, int N, int K, const void* h_in, void
   return DL_OK;
 }
 
+extern "C" int dl_gemv_gu_tp_pk(const void* data, int64_t data_bytes, const void* hdr, int64_t hdr_rows, const void* pool, int64_t pool_spans, int hb, int N, int K,
+                                const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y, const dl_tp_weights* tp, int d_model,
+                                void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base, void* granules, int call_tag, int32_t* err_flag,
+                                int dtype, int grid_cap, void* stream) {
+  DL_REQUIRE(h_in && norm_w && y && tp && tp_workspace && decision && pos_base && granules, "dl_gemv_gu_tp_pk: NULL pointer");
+  DL_REQUIRE(dtype == DL_BF16, "dl_gemv_gu_tp_pk: bf16 only (dtype %d)", dtype);
+  DL_REQUIRE(N > 0 && N % 2 == 0 && K > 0 && d_model > 0 && d_model % 32 == 0 && K <= 5120, "dl_gemv_gu_tp_pk: bad shape N=%d K=%d d_model=%d", N, K, d_model);
+  DL_REQUIRE(K % 1024 == 0 && K <= 8192, "dl_gemv_gu_tp_pk: packed rows take K %% 1024 == 0, K <= 8192 (K=%d)", K);
+  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_gu_tp_pk: h_out must be a distinct buffer when delta is given");
+  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_gu_tp_pk: call_tag / grid_cap must be >= 0");
+  GuTpPkArgs a;
+  if (const int rc = pk_mat_check("dl_gemv_gu_tp_pk", a.m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, N, K)) return rc;
+  if (grid_cap == 0) grid_cap = kGemvGridCap;
+  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = y; a.N = N; a.K = K; a.eps = eps;
+  a.w = *tp; a.tp_ws = reinterpret_cast<float*>(tp_workspace); a.logits = logits_out; a.decision = decision; a.pos_base = pos_base;
+  a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag; a.D = d_model; a.call_tag = call_tag;
+  // the grid and the LDS size are dl_gemv_gu_tp's
+  const int side = (d_model + 7) / 8 + (d_model / 2 + 7) / 8 + 1;
+  const int groups = (N / 2 + 3) / 4;
+  if (grid_cap > 2 * side) grid_cap -= side;
+  const int grid = (groups < grid_cap ? groups : grid_cap) + side;
+  size_t smem = (size_t)K * sizeof(float);
+  if (smem < (size_t)2 * d_model * sizeof(float)) smem = (size_t)2 * d_model * sizeof(float);
+  hipStream_t st = as_stream(stream);
+  if (K / 8 <= 64 * 8) hipLaunchKernelGGL((gemv_gu_tp_kernel<bf16_t, 8, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  else hipLaunchKernelGGL((gemv_gu_tp_kernel<bf16_t, 10, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  DL_CHECK_LAUNCH("dl_gemv_gu_tp_pk");
+  return DL_OK;
+}
+
 extern "C" int64_t dl_gemv_qkv_attn_workspace_bytes(int n_heads, int n_kv_heads, int head_dim) {
   // the projection's N granules + the partials of the secondary attention workgroups: [head][kQaMaxSplits - 1][M, L, O[head_dim]]
   return ((int64_t)(n_heads + 2 * n_kv_heads) * head_dim + (int64_t)n_heads * (kQaMaxSplits - 1) * (head_dim + 2)) * (int64_t)sizeof(u64_t);
@@ -705,6 +759,45 @@ extern "C" int dl_gemv_qkv_attn(const void* W, int K, const void* h_in, void* h_
   return DL_OK;
 }
 
+extern "C" int dl_gemv_qkv_attn_pk(const void* data, int64_t data_bytes, const void* hdr, int64_t hdr_rows, const void* pool, int64_t pool_spans, int hb, int K,
+                                   const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* qkv, const void* cos_tab, const void* sin_tab,
+                                   int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab, void* v_slab, int64_t slab_stride_b, int64_t slab_stride_h,
+                                   int T_cap, void* out, void* granules, int call_tag, int32_t* err_flag, int n_splits, int n_heads, int n_kv_heads, int head_dim,
+                                   int dtype, int grid_cap, void* stream) {
+  DL_REQUIRE(h_in && norm_w && qkv && cos_tab && sin_tab && pos_base && kv_len && k_slab && v_slab && out && granules, "dl_gemv_qkv_attn_pk: NULL pointer");
+  DL_REQUIRE(dtype == DL_BF16, "dl_gemv_qkv_attn_pk: bf16 only (dtype %d)", dtype);
+  DL_REQUIRE(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && (head_dim == 128 || head_dim == 64) && K > 0 && n_pos > 0 && T_cap > 0,
+             "dl_gemv_qkv_attn_pk: bad shape");
+  DL_REQUIRE(K % 1024 == 0 && K <= 8192, "dl_gemv_qkv_attn_pk: packed rows take K %% 1024 == 0, K <= 8192 (K=%d)", K);
+  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_qkv_attn_pk: h_out must be a distinct buffer when delta is given");
+  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_qkv_attn_pk: call_tag / grid_cap must be >= 0");
+  DL_REQUIRE(n_splits >= 1 && n_splits <= kQaMaxSplits, "dl_gemv_qkv_attn_pk: n_splits=%d must be in [1, %d]", n_splits, kQaMaxSplits);
+  const int N = (n_heads + 2 * n_kv_heads) * head_dim;
+  QkvAttnPkArgs a;
+  if (const int rc = pk_mat_check("dl_gemv_qkv_attn_pk", a.m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, N, K)) return rc;
+  if (grid_cap == 0) grid_cap = kGemvGridCap;
+  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = qkv; a.N = N; a.K = K; a.eps = eps;
+  a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.pos_base = pos_base; a.kv_len = kv_len; a.k_slab = k_slab; a.v_slab = v_slab; a.out = out;
+  a.stride_b = slab_stride_b; a.stride_h = slab_stride_h; a.n_pos = n_pos; a.T_cap = T_cap; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads;
+  a.call_tag = call_tag; a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag;
+  a.n_splits = n_splits;  // (the attention workgroups and their key chunks: as dl_gemv_qkv_attn)
+  a.chunk_keys = n_splits == 1 ? 256 : 128;
+  const int n_attn = n_heads * n_splits;
+  const int groups = (N + 4 * kQaPkR - 1) / (4 * kQaPkR);
+  if (grid_cap > 2 * n_attn) grid_cap -= n_attn;  // projection + attention workgroups together stay within what is resident at once
+  const int grid = (groups < grid_cap ? groups : grid_cap) + n_attn;
+  const size_t smem = (size_t)K * 2;
+  hipStream_t st = as_stream(stream);
+  if (n_splits == 1) {
+    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 128, false, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 64, false, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  } else {
+    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 128, true, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 64, true, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  }
+  DL_CHECK_LAUNCH("dl_gemv_qkv_attn_pk");
+  return DL_OK;
+}
 
 extern "C" int dl_gemv_max_batch(int K, int dtype) {
   const int es = dtype == DL_F32 ? 4 : 2;

@@ -12,155 +12,10 @@
 //
 // No lane ever forms an address outside the row it reads: pairs of full spans are read by all 64 lanes (16 + 8 bytes each), what is left of a
 // segment is read per chunk (8 + 4 bytes) under `chunk < row end`; row indices -- of the prefetched headers too -- are clamped to N - 1.
-#include "gemv_dot.h"
-#include "gemv_prologue.h"
-#include "../../include/dynllava.h"
+// The packed helpers (PkMat, pk_decode, pk_request_*, pk_pass_dot) and the add + rmsnorm body live in gemv_pk.h, which gemv.hip includes too.
+#include "gemv_pk.h"
 
 namespace dl {
-
-constexpr int kPkPairBytes = 1536;  // two spans: 64 x 16 low bytes + 64 x 8 nibble bytes
-constexpr int kPkSpanBytes = 1024;  // a raw span in the pool
-
-struct PkMat {
-  const unsigned char* data;  // [N][K * 3 / 2]
-  const uint2* hdr;           // [N] {span mask, first pool span}
-  const unsigned char* pool;  // [pool_last + 1][1024]
-  int64_t row_bytes;
-  uint32_t pool_last;
-  uint32_t hb4;  // hb in every byte
-};
-
-__device__ __forceinline__ uint2 ldg_nt8(const void* p) {
-  typedef uint32_t u32x2_t __attribute__((ext_vector_type(2)));
-  const u32x2_t r = __builtin_nontemporal_load(reinterpret_cast<const u32x2_t*>(p));
-  return make_uint2(r.x, r.y);
-}
-__device__ __forceinline__ uint32_t ldg_nt4(const void* p) { return __builtin_nontemporal_load(reinterpret_cast<const uint32_t*>(p)); }
-
-// the low bytes of 8 elements (lo0: 0..3, lo1: 4..7) and their 4 pre-spread nibble bytes -> the 16-byte bf16 chunk
-__device__ __forceinline__ uint4 pk_decode(uint32_t lo0, uint32_t lo1, uint32_t nb, uint32_t hb4) {
-  const uint32_t h0 = ((nb & 0x07070707u) + hb4) | ((nb & 0x08080808u) << 4);
-  const uint32_t h1 = (((nb >> 4) & 0x07070707u) + hb4) | (nb & 0x80808080u);
-  // v_perm_b32: selector bytes 0..3 take the second operand's bytes, 4..7 the first's
-  return make_uint4(__builtin_amdgcn_perm(h0, lo0, 0x05010400u), __builtin_amdgcn_perm(h0, lo0, 0x07030602u),
-                    __builtin_amdgcn_perm(h1, lo1, 0x05010400u), __builtin_amdgcn_perm(h1, lo1, 0x07030602u));
-}
-
-// A row's header as wave-uniform scalars
-struct PkHdr {
-  uint32_t mask, off;
-};
-__device__ __forceinline__ PkHdr pk_uniform(const uint2 h) {
-  PkHdr r;
-  r.mask = __builtin_amdgcn_readfirstlane(h.x);
-  r.off = __builtin_amdgcn_readfirstlane(h.y);
-  return r;
-}
-// the lane's 16 bytes of span s of a row whose header is h (s is flagged in h.mask)
-__device__ __forceinline__ const unsigned char* pk_raw_addr(const PkMat& m, const PkHdr& h, int s, int lane) {
-  uint32_t idx = h.off + (uint32_t)__builtin_popcount(h.mask & ((1u << s) - 1u));
-  idx = idx < m.pool_last ? idx : m.pool_last;
-  return m.pool + (int64_t)idx * kPkSpanBytes + lane * 16;
-}
-
-// A *slot* is a pair of spans of one row in flight: chunks c = 2 slot (lo.x, lo.y, nb.x) and 2 slot + 1 (lo.z, lo.w, nb.y).  A *pass* holds SLOTS slots of
-// each of R rows, requested slot-major (the order they are consumed in), the rows' flagged spans of the pass and the raw chunk of each row's first.
-template <int R, int SLOTS>
-struct PkPass {
-  uint4 lo[SLOTS][R];
-  uint2 nb[SLOTS][R];
-  uint4 raw0[R];
-  uint32_t fm[R];
-};
-
-// Requests the lane's bytes of pair `p` of a segment (`seg`: its first byte, nc chunks).  TAIL: the segment may end in fewer than 128 chunks, which are
-// read per chunk (lanes past the end read nothing and hold zeros: they decode to a finite positive number, and their x is zero).
-template <bool TAIL>
-__device__ __forceinline__ void pk_request_slot(uint4& lo, uint2& nb, const unsigned char* seg, int nc, int p, int lane) {
-  const int P = nc >> 7;
-  if (!TAIL || p < P) {  // (TAIL = false: the caller knows that pair p exists)
-    lo = ldg_nt(seg + (int64_t)p * kPkPairBytes + lane * 16);
-    nb = ldg_nt8(seg + (int64_t)p * kPkPairBytes + 1024 + lane * 8);
-  } else {  // at most ONE slot of a segment is not a whole pair: the nt < 128 chunks behind the pairs, read by lanes t < nt (and t + 64 < nt)
-    const int nt = nc - 128 * P;
-    const unsigned char* tail = seg + (int64_t)P * kPkPairBytes;
-    uint2 l0 = make_uint2(0u, 0u), l1 = make_uint2(0u, 0u);
-    uint32_t n0 = 0u, n1 = 0u;
-    if (p == P && lane < nt) {
-      l0 = ldg_nt8(tail + lane * 8);
-      n0 = ldg_nt4(tail + nt * 8 + lane * 4);
-    }
-    if (p == P && lane + 64 < nt) {
-      l1 = ldg_nt8(tail + (lane + 64) * 8);
-      n1 = ldg_nt4(tail + nt * 8 + (lane + 64) * 4);
-    }
-    lo = make_uint4(l0.x, l0.y, l1.x, l1.y);
-    nb = make_uint2(n0, n1);
-  }
-}
-
-// The flagged spans of each row among the pass's 2 SLOTS spans from span s0 on (bit c: chunk slot c; nsp: spans of the segment left from s0 on -- a later
-// span belongs to another wave), and the request for the raw chunk of the first one.
-template <int R, int SLOTS>
-__device__ __forceinline__ void pk_request_raw(PkPass<R, SLOTS>& ps, const PkMat& m, const PkHdr (&h)[R], int s0, int nsp, int lane) {
-  const uint32_t keep = nsp >= 2 * SLOTS ? ((1u << (2 * SLOTS)) - 1u) : ((1u << nsp) - 1u);
-#pragma unroll
-  for (int r = 0; r < R; ++r) {
-    ps.fm[r] = (h[r].mask >> s0) & keep;
-    ps.raw0[r] = make_uint4(0u, 0u, 0u, 0u);
-    if (ps.fm[r] != 0u) ps.raw0[r] = ldg_nt(pk_raw_addr(m, h[r], s0 + __builtin_ctz(ps.fm[r]), lane));
-  }
-}
-
-// acc[r] += the pass's chunks of row r . x, in rising chunk order; slots [0, nvalid).  x(c): the x chunk of chunk slot c.  The usual pass (no flagged
-// span in any row) is straight-line code, held slot by slot to the order decode -> dot so that the decoded words of later slots do not pile up in registers.
-template <int R, int SLOTS, typename XF>
-__device__ __forceinline__ void pk_pass_dot(const PkMat& m, const PkPass<R, SLOTS>& ps, const PkHdr (&h)[R], int s0, int nvalid, int lane, float (&acc)[R], XF x) {
-  uint32_t any = 0u;
-#pragma unroll
-  for (int r = 0; r < R; ++r) any |= ps.fm[r];
-  if (any == 0u) {
-#pragma unroll
-    for (int i = 0; i < SLOTS; ++i) {
-      if (i < nvalid) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const uint4 xv = x(2 * i + j);
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const uint4& lo = ps.lo[i][r];
-            const uint2& nb = ps.nb[i][r];
-            const uint4 w = j ? pk_decode(lo.z, lo.w, nb.y, m.hb4) : pk_decode(lo.x, lo.y, nb.x, m.hb4);
-            acc[r] = dot16<bf16_t>(w, xv, acc[r]);
-          }
-        }
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  } else {
-    int first[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) first[r] = ps.fm[r] ? __builtin_ctz(ps.fm[r]) : -1;
-#pragma unroll
-    for (int i = 0; i < SLOTS; ++i) {
-      if (i < nvalid) {
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int c = 2 * i + j;
-          const uint4 xv = x(c);
-#pragma unroll
-          for (int r = 0; r < R; ++r) {
-            const uint4& lo = ps.lo[i][r];
-            const uint2& nb = ps.nb[i][r];
-            uint4 w = j ? pk_decode(lo.z, lo.w, nb.y, m.hb4) : pk_decode(lo.x, lo.y, nb.x, m.hb4);
-            if ((ps.fm[r] >> c) & 1u) w = c == first[r] ? ps.raw0[r] : ldg_nt(pk_raw_addr(m, h[r], s0 + c, lane));  // (wave-uniform)
-            acc[r] = dot16<bf16_t>(w, xv, acc[r]);
-          }
-        }
-      }
-    }
-  }
-}
 
 // ---- plain prologue, x in registers (o_proj; K <= 8192): gemv_b1_plain_kernel on packed rows.  RW rows per wave and pass share the x registers,
 // which keeps at least as many bytes in flight per lane as the bf16 kernel's one row (RW * XB * 96 against XB * 128) ----
@@ -288,83 +143,7 @@ template <bool PAIR>
 __global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemv_pk_addnorm_kernel(PkMat m, int N, int K, const void* __restrict__ h_,
                                                                                                             void* __restrict__ h_out_, const void* __restrict__ delta_,
                                                                                                             const void* __restrict__ nw_, float eps, void* __restrict__ y_) {
-  constexpr int R = 2, SLOTS = 4, PRE = 2;
-  using S = Elem<bf16_t>::storage;
-  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  S* xs = reinterpret_cast<S*>(smem);  // [K]
-  __shared__ float red[4];
-  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // (a scalar: row addresses stay in SGPRs)
-  const int bid = blockIdx.x, nblk = gridDim.x;
-  const int nvec = K / 8, P = nvec >> 7;
-  const int n_out = PAIR ? N / 2 : N;
-  constexpr int RW = PAIR ? 1 : R;
-  const int groups = (n_out + 4 * RW - 1) / (4 * RW);
-  auto row_of = [&](int grp, int r) {  // gemv_body's row choice
-    const int n0 = grp * 4 * RW + wid * RW;
-    int n = PAIR ? (n0 + r * n_out) : (n0 + r);
-    n = n < N ? n : N - 1;
-    if (PAIR && n0 >= n_out) n = r * n_out;
-    return n;
-  };
-  // the weight stream starts BEFORE the prologue (as in gemv_body): the first pairs and the headers of this workgroup's first rows
-  PkPass<R, SLOTS> ps;
-  uint2 hraw[R];
-  const bool have_pre = bid < groups;
-  if (have_pre) {
-#pragma unroll
-    for (int r = 0; r < R; ++r) hraw[r] = m.hdr[row_of(bid, r)];
-#pragma unroll
-    for (int i = 0; i < PRE; ++i)
-      if (i < P) {
-#pragma unroll
-        for (int r = 0; r < R; ++r) pk_request_slot<false>(ps.lo[i][r], ps.nb[i][r], m.data + (int64_t)row_of(bid, r) * m.row_bytes, nvec, i, lane);
-      }
-  }
-  gemv_build_x<bf16_t, 1, 1>(xs, red, K, nullptr, 0, h_, h_out_, delta_, nw_, eps, bid);
-  __syncthreads();
-
-  bool first = have_pre;
-  for (int grp = bid; grp < groups; grp += nblk) {
-    const int n0 = grp * 4 * RW + wid * RW;
-    const unsigned char* wp[R];
-    PkHdr h[R];
-    float acc[R];
-#pragma unroll
-    for (int r = 0; r < R; ++r) {
-      wp[r] = m.data + (int64_t)row_of(grp, r) * m.row_bytes;
-      h[r] = pk_uniform(hraw[r]);
-      acc[r] = 0.f;
-    }
-    const int nxt = grp + nblk < groups ? grp + nblk : grp;
-    for (int p0 = 0; p0 < P; p0 += SLOTS) {
-      const int i0 = first ? PRE : 0;  // the first slots of the workgroup's first pass are in flight since before the prologue
-      first = false;
-#pragma unroll
-      for (int i = 0; i < SLOTS; ++i)
-        if (i >= i0 && p0 + i < P) {
-#pragma unroll
-          for (int r = 0; r < R; ++r) pk_request_slot<false>(ps.lo[i][r], ps.nb[i][r], wp[r], nvec, p0 + i, lane);
-        }
-      pk_request_raw<R, SLOTS>(ps, m, h, 2 * p0, 2 * (P - p0), lane);
-      if (p0 == 0) {  // the next rows' headers travel with this pass's weights
-#pragma unroll
-        for (int r = 0; r < R; ++r) hraw[r] = m.hdr[row_of(nxt, r)];
-      }
-      pk_pass_dot<R, SLOTS>(m, ps, h, 2 * p0, P - p0, lane, acc,
-                            [&](int c) { return *reinterpret_cast<const uint4*>(xs + (int64_t)(lane + 64 * (2 * p0 + c)) * 8); });
-    }
-#pragma unroll
-    for (int r = 0; r < R; ++r) acc[r] = wave_sum(acc[r]);
-    if (lane == 0) {
-      if constexpr (PAIR) {
-        if (n0 < n_out) store1<bf16_t>(y_, n0, gemv_silu_pair<bf16_t>(acc[0], acc[1]));
-      } else {
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-          if (n0 + r < N) store1<bf16_t>(y_, n0 + r, acc[r]);
-      }
-    }
-  }
+  gemv_pk_body<PAIR, 2, 4, 2>(m, N, K, h_, h_out_, delta_, nw_, eps, y_, (int)blockIdx.x, (int)gridDim.x, nullptr, 0u);
 }
 
 constexpr int kPkGridCap = 1024;  // dl_gemv's default: 4 workgroups per CU
@@ -379,25 +158,14 @@ extern "C" int dl_gemv_pk(int mode, const void* data, int64_t data_bytes, const 
   DL_REQUIRE(data && hdr && pool && y, "dl_gemv_pk: NULL pointer");
   DL_REQUIRE(dtype == DL_BF16, "dl_gemv_pk: bf16 only (dtype %d)", dtype);
   DL_REQUIRE(B == 1, "dl_gemv_pk: batch 1 only (B=%d)", B);
-  DL_REQUIRE(N > 0 && K > 0 && K % 64 == 0 && K <= 16384 && grid_cap >= 0, "dl_gemv_pk: bad shape N=%d K=%d", N, K);
-  DL_REQUIRE(hb >= 0 && hb <= 120, "dl_gemv_pk: hb=%d is outside [0, 120]", hb);
-  const int64_t row_bytes = (int64_t)K * 3 / 2;
-  DL_REQUIRE(data_bytes >= (int64_t)N * row_bytes, "dl_gemv_pk: %lld packed bytes, %d rows of K=%d need %lld", (long long)data_bytes, N, K, (long long)((int64_t)N * row_bytes));
-  DL_REQUIRE(hdr_rows >= N, "dl_gemv_pk: %lld row headers for %d rows", (long long)hdr_rows, N);
-  DL_REQUIRE(pool_spans >= 1 && pool_spans < ((int64_t)1 << 31), "dl_gemv_pk: the pool must hold at least one span (%lld)", (long long)pool_spans);
-  DL_REQUIRE(((uintptr_t)data | (uintptr_t)pool) % 16 == 0 && (uintptr_t)hdr % 8 == 0, "dl_gemv_pk: data / pool must be 16-byte aligned, hdr 8-byte");
+  DL_REQUIRE(grid_cap >= 0, "dl_gemv_pk: bad grid_cap %d", grid_cap);
+  PkMat m;
+  if (const int rc = pk_mat_check("dl_gemv_pk", m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, N, K)) return rc;
   const int pro = mode & 3;
   const bool pair = (mode & DL_GEMV_OUT_SILU_PAIR) != 0;
   DL_REQUIRE((mode & ~(3 | DL_GEMV_OUT_SILU_PAIR)) == 0 && (pro == DL_GEMV_PLAIN || pro == DL_GEMV_ADDNORM), "dl_gemv_pk: bad mode %d", mode);
   DL_REQUIRE(!pair || (pro == DL_GEMV_ADDNORM && N % 2 == 0), "dl_gemv_pk: SILU_PAIR needs the ADDNORM prologue and an even N");
   if (grid_cap == 0) grid_cap = kPkGridCap;
-  PkMat m;
-  m.data = reinterpret_cast<const unsigned char*>(data);
-  m.hdr = reinterpret_cast<const uint2*>(hdr);
-  m.pool = reinterpret_cast<const unsigned char*>(pool);
-  m.row_bytes = row_bytes;
-  m.pool_last = (uint32_t)(pool_spans - 1);
-  m.hb4 = (uint32_t)hb * 0x01010101u;
   hipStream_t st = as_stream(stream);
   if (pro == DL_GEMV_ADDNORM) {
     DL_REQUIRE(h_in && norm_w, "dl_gemv_pk: missing operand for mode %d", mode);

@@ -161,6 +161,7 @@ class DecodeScheduler:
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
             pk = (getattr(layer, "pk", None) or no_pk) if pack else no_pk
+            pk_qkv = getattr(layer, "pk_qkv", None) if pack and self.decode_weight_pack_qkv else None
             if mx8:
                 self._decode_layer_mx8(st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp)
                 if delta is not None:
@@ -174,10 +175,20 @@ class DecodeScheduler:
             # False, as the kernel tests set it); by default the stand-alone single-split launch of a small batch runs eight waves -- another
             # (equally valid) summation order, so DL_FUSE_QKV_ATTN=0 is an A/B of speed, not of bits (tokens / KV lengths: tested equal)
             fused_attn = self.fuse_qkv_attn and st.B == 1 and ns == 1 and st.qa_gran is not None and cache.kv_format is None
-            if fused_attn:
+            if fused_attn and pk_qkv is not None:
+                ops.gemv_qkv_attn_pk(pk_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
+                                     st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
+                                     n_splits=cache.fused_attn_splits(i, self.fused_attn_max_splits))
+                if delta is not None:
+                    h_cur, h_alt = h_alt, h_cur
+            elif fused_attn:
                 ops.gemv_qkv_attn(layer.w_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
                                   st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
                                   n_splits=cache.fused_attn_splits(i, self.fused_attn_max_splits))
+                if delta is not None:
+                    h_cur, h_alt = h_alt, h_cur
+            elif pk_qkv is not None:
+                ops.gemv_pk(pk_qkv, st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
                 if delta is not None:
                     h_cur, h_alt = h_alt, h_cur
             else:
@@ -204,7 +215,11 @@ class DecodeScheduler:
                 ops.gemv_pk(pk["o"], st.o, x=st.attn)
             else:
                 ops.gemv(layer.self_attn.o_proj.weight, st.o, x=st.attn)
-            if fused_tp:  # (this one layer keeps the model-dtype weights: the launch carries the predictor)
+            if fused_tp and pk["gu"] is not None:
+                tp = self.model.output_text_score_predictor
+                ops.gemv_gu_tp_pk(pk["gu"], st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
+                                  st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
+            elif fused_tp:
                 tp = self.model.output_text_score_predictor
                 ops.gemv_gu_tp(layer.w_gu, st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
                                st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
@@ -449,7 +464,7 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.decode_weight_pack, self.decode_weight_pack_plain, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
+               self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
                self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured; the sampling parameters and the labels are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):

@@ -115,6 +115,10 @@ SIGNATURES = {
                               c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "dl_gemv_qkv_attn": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                  c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dl_gemv_qkv_attn_pk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p,
+                                    c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dl_gemv_gu_tp_pk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(TpWeights),
+                                 c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "dl_attn_policy_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int]),
     "dl_attn_policy_fwd": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
@@ -788,6 +792,33 @@ def gemv_qkv_attn(w, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, k
     return out
 
 
+def _pk_args(p):
+    """(data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb) of a bf16pack.PackedBf16, as dl_gemv_pk and the fused packed launches take them."""
+    assert p.data.dtype == torch.uint8 and p.pool.dtype == torch.uint8 and p.hdr.dtype == torch.int32 and p.data.is_contiguous() and p.hdr.is_contiguous() and p.pool.is_contiguous()
+    return _p(p.data), p.data.numel(), _p(p.hdr), p.hdr.shape[0], _p(p.pool), p.pool.numel() // 1024, int(p.hb)
+
+
+def gemv_qkv_attn_pk(p, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim,
+                     err=None, grid_cap=0, n_splits=1):
+    """gemv_qkv_attn() on a losslessly packed q|k|v matrix (p: bf16pack.PackedBf16 of w [N,K]): bit-identical outputs, 0.79 of the weight bytes."""
+    _dev(p.data, p.hdr, p.pool, qkv, h_in, h_out, delta, norm_w, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, err)
+    N, K = p.N, p.K
+    assert qkv.dtype == torch.bfloat16 and qkv.shape == (1, N) and qkv.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
+    assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
+    assert out.shape == (1, n_heads * head_dim) and out.is_contiguous() and N == (n_heads + 2 * n_kv_heads) * head_dim
+    assert pos_base.dtype == torch.int32 and kv_len.dtype == torch.int32 and granules.numel() * granules.element_size() >= lib().dl_gemv_qkv_attn_workspace_bytes(int(n_heads), int(n_kv_heads), int(head_dim))
+    assert k_slab.stride(3) == 1 and k_slab.stride(2) == head_dim and k_slab.stride() == v_slab.stride()
+    sb, sh = k_slab.stride(0), k_slab.stride(1)
+    _check(
+        lib().dl_gemv_qkv_attn_pk(
+            *_pk_args(p), K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(qkv), _p(cos), _p(sin), cos.shape[0], _p(pos_base), _p(kv_len), _p(k_slab), _p(v_slab), sb, sh,
+            k_slab.shape[2], _p(out), _p(granules), int(call_tag), _p(err), int(n_splits), int(n_heads), int(n_kv_heads), int(head_dim), dtype_code(qkv.dtype), int(grid_cap), _stream(),
+        ),
+        "dl_gemv_qkv_attn_pk",
+    )
+    return out
+
+
 def gemv_gu_tp_workspace(d_model, device):
     """Granule buffer of gemv_gu_tp (zeroed: no tag is 0); zero it again at the start of every request."""
     return torch.zeros(int(lib().dl_gemv_gu_tp_workspace_bytes(int(d_model))) // 8, dtype=torch.int64, device=device)
@@ -805,6 +836,22 @@ def gemv_gu_tp(w, y, h_in, h_out, delta, norm_w, eps, tp_weights: TpWeights, d_m
         lib().dl_gemv_gu_tp(_p(w), N, K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), ctypes.byref(tp_weights), int(d_model), _p(tp_workspace), _p(logits_out),
                             _p(decision), _p(pos_base), _p(granules), int(call_tag), _p(err), dtype_code(w.dtype), int(grid_cap), _stream()),
         "dl_gemv_gu_tp",
+    )
+    return y
+
+
+def gemv_gu_tp_pk(p, y, h_in, h_out, delta, norm_w, eps, tp_weights: TpWeights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err=None, grid_cap=0):
+    """gemv_gu_tp() on a losslessly packed gate|up matrix (p: bf16pack.PackedBf16 of w [N,K]): bit-identical outputs."""
+    _dev(p.data, p.hdr, p.pool, y, h_in, h_out, delta, norm_w, tp_workspace, logits_out, decision, pos_base, granules, err)
+    N, K = p.N, p.K
+    assert y.dtype == torch.bfloat16 and y.shape == (1, N // 2) and y.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
+    assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
+    assert decision.dtype == torch.int32 and pos_base.dtype == torch.int32 and tp_workspace.dtype == torch.float32
+    assert tp_workspace.numel() * 4 >= lib().dl_text_predictor_workspace_bytes(1, d_model) and granules.numel() * granules.element_size() >= lib().dl_gemv_gu_tp_workspace_bytes(d_model)
+    _check(
+        lib().dl_gemv_gu_tp_pk(*_pk_args(p), N, K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), ctypes.byref(tp_weights), int(d_model), _p(tp_workspace), _p(logits_out),
+                               _p(decision), _p(pos_base), _p(granules), int(call_tag), _p(err), dtype_code(y.dtype), int(grid_cap), _stream()),
+        "dl_gemv_gu_tp_pk",
     )
     return y
 

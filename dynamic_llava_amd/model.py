@@ -80,6 +80,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         # ... o_proj and down_proj too.  Off: their packed launches (x in registers, one short stream per launch) measured no faster than the bf16 ones
         # (o 6.8 vs 6.7 us, down 17.0 vs 16.3 us), so only gate|up and the vocabulary projection are packed by default
         self.decode_weight_pack_plain = os.environ.get("DL_WEIGHT_PACK_PLAIN", "0") == "1"
+        # ... and every layer's q|k|v, which streams inside the fused q|k|v + attention launch (dl_gemv_qkv_attn_pk; the unfused launch: dl_gemv_pk).  The copy is
+        # kept as layer.pk_qkv, beside layer.pk.  DL_WEIGHT_PACK_QKV=0: not made, not used (+2.5 GB of copies at 7B when on)
+        self.decode_weight_pack_qkv = os.environ.get("DL_WEIGHT_PACK_QKV", "1") == "1"
         # attention workgroups per head inside the fused launch: up to this many, one per 128 keys of the scheduled bound (DL_QA_SPLITS=1: always one)
         self.fused_attn_max_splits = max(1, min(4, int(os.environ.get("DL_QA_SPLITS", "4"))))  # the kernel takes 1..4 (kQaMaxSplits)
         self.gu_grid_cap = int(os.environ.get("DL_GU_GRID", "0"))  # workgroups of the batch-1 gate|up launch (0: the kernel's default, 1024)
@@ -267,11 +270,13 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         """The 12-bit packed copies (bf16pack.pack) of the matrices the batch-1 decode step streams through dl_gemv_pk: every layer's gate|up and the vocabulary
         projection; with decode_weight_pack_plain also o_proj and down_proj.  Rebuilt by every finalize() -- i.e. whenever the weight fingerprint (lm_head included) moves -- and dropped
         for MXFP8 decoder weights, whose step streams the codes.  A matrix the kernel does not take (gemv_pk_ok) or that would not shrink below 0.9 of its
-        size (pack() returns None) keeps its model-dtype launch.  q|k|v stays in the model dtype (the fused q|k|v + attention launch)."""
+        size (pack() returns None) keeps its model-dtype launch.  With decode_weight_pack_qkv every layer's q|k|v is packed too, under the same rules, as
+        layer.pk_qkv (not part of layer.pk: the fused q|k|v + attention launch streams it through dl_gemv_qkv_attn_pk)."""
         from . import bf16pack
 
         for l in self.model.layers:
             l.pk = None
+            l.pk_qkv = None
         self._pk_lm_head = None
         if not self.decode_weight_pack or self.decode_weight_format is not None or self.dtype != torch.bfloat16:
             return
@@ -281,6 +286,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         for l in self.model.layers:
             l.pk = {"o": pk(l.self_attn.o_proj.weight.data, ops.GEMV_PLAIN) if plain else None, "gu": pk(l.w_gu, A),
                     "down": pk(l.mlp.down_proj.weight.data, ops.GEMV_PLAIN) if plain else None}
+            if self.decode_weight_pack_qkv:
+                l.pk_qkv = pk(l.w_qkv, A)
         self._pk_lm_head = pk(self.lm_head.weight.data, A)
 
     def weight_pack_bytes(self) -> dict:
@@ -290,7 +297,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         ps = [p for l in self.model.layers for p in (getattr(l, "pk", None) or {}).values() if p is not None]
         if getattr(self, "_pk_lm_head", None) is not None:
             ps.append(self._pk_lm_head)
-        return {"matrices": len(ps), "packed": sum(bf16pack.packed_nbytes(p) for p in ps), "bf16": sum(bf16pack.raw_nbytes(p) for p in ps)}
+        qs = [l.pk_qkv for l in self.model.layers if getattr(l, "pk_qkv", None) is not None]
+        return {"matrices": len(ps), "packed": sum(bf16pack.packed_nbytes(p) for p in ps), "bf16": sum(bf16pack.raw_nbytes(p) for p in ps),
+                "qkv": {"matrices": len(qs), "packed": sum(bf16pack.packed_nbytes(p) for p in qs), "bf16": sum(bf16pack.raw_nbytes(p) for p in qs)}}
 
     def _quantize_decoder_weights(self):
         from .mxfp8 import dequantize_mx8
@@ -396,7 +405,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         return {
             "use_hip_graph": self.use_hip_graph, "attn_inkernel_combine": self.attn_inkernel_combine, "device_prompt_layout": self.device_prompt_layout,
             "tp_side_stream": self.tp_side_stream, "gemv_max_decode_batch": self.gemv_max_decode_batch, "smallm_max_decode_batch": self.smallm_max_decode_batch,
-            "fuse_qkv_attn": self.fuse_qkv_attn, "fuse_gu_tp": self.fuse_gu_tp, "decode_weight_pack": self.decode_weight_pack, "decode_weight_pack_plain": self.decode_weight_pack_plain, "fused_attn_max_splits": self.fused_attn_max_splits, "gu_grid_cap": self.gu_grid_cap,
+            "fuse_qkv_attn": self.fuse_qkv_attn, "fuse_gu_tp": self.fuse_gu_tp, "decode_weight_pack": self.decode_weight_pack, "decode_weight_pack_plain": self.decode_weight_pack_plain, "decode_weight_pack_qkv": self.decode_weight_pack_qkv, "fused_attn_max_splits": self.fused_attn_max_splits, "gu_grid_cap": self.gu_grid_cap,
             "qkv_attn_grid_cap": self.qkv_attn_grid_cap, "splitk_o_proj": self.splitk_o_proj, "packed_prefill_gemm": self.packed_prefill_gemm, "packed_down_proj": self.packed_down_proj, "packed_qkv_parts": self.packed_qkv_parts, "packed_decode_mlp": self.packed_decode_mlp, "packed_decode_mlp_min_batch": self.packed_decode_mlp_min_batch, "packed_decode_qkv_min_batch": self.packed_decode_qkv_min_batch, "packed_decode_qkv_parts": self.packed_decode_qkv_parts, "packed_decode_qkv_parts_max_batch": self.packed_decode_qkv_parts_max_batch,
             "smallm_wide_slices": self.smallm_wide_slices, "decode_sync_every": self.decode_sync_every, "prefill_width_bucket": self.prefill_width_bucket,
             "max_prefill_graphs": self.max_prefill_graphs,

@@ -518,6 +518,15 @@ int dl_gemv_qkv_attn(const void* W, int K, const void* h_in, void* h_out, const 
                      const void* cos_tab, const void* sin_tab, int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab,
                      void* v_slab, int64_t slab_stride_b, int64_t slab_stride_h, int T_cap, void* out, void* granules, int call_tag,
                      int32_t* err_flag, int n_splits, int n_heads, int n_kv_heads, int head_dim, int dtype, int grid_cap, void* stream);
+/* dl_gemv_qkv_attn with the projection matrix given as its lossless 12-bit packed copy (dl_gemv_pk's format and arguments: data, data_bytes, hdr, hdr_rows,
+ * pool, pool_spans, hb) in place of W: the projection workgroups stream 0.79 of the bytes, everything the launch writes (qkv, h_out, the appended K/V row,
+ * out) is bit-identical to dl_gemv_qkv_attn on the unpacked matrix.  bf16 only, K % 1024 == 0, K <= 8192; the packed operands are checked as dl_gemv_pk
+ * checks them (DL_ERR_ARG, nothing is launched) and no header content makes the kernel read outside data / hdr / pool. */
+int dl_gemv_qkv_attn_pk(const void* data, int64_t data_bytes, const void* hdr, int64_t hdr_rows, const void* pool, int64_t pool_spans, int hb, int K,
+                        const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* qkv, const void* cos_tab, const void* sin_tab,
+                        int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab, void* v_slab, int64_t slab_stride_b, int64_t slab_stride_h,
+                        int T_cap, void* out, void* granules, int call_tag, int32_t* err_flag, int n_splits, int n_heads, int n_kv_heads, int head_dim,
+                        int dtype, int grid_cap, void* stream);
 
 /* ---- the gate|up projection of layer `sparse_layer` at decode batch 1 (dl_gemv ADDNORM | OUT_SILU_PAIR: DML:1289 + DML:134-139 + DML:328) AND the
  * text predictor (dl_text_predictor_decide: DML:1385-1387, 2388-2391) on the residual stream entering that layer -- the h_in of this launch --
@@ -529,6 +538,12 @@ int64_t dl_gemv_gu_tp_workspace_bytes(int d_model);
 int dl_gemv_gu_tp(const void* W, int N, int K, const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y,
                   const dl_tp_weights* tp, int d_model, void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base,
                   void* granules, int call_tag, int32_t* err_flag, int dtype, int grid_cap, void* stream);
+/* dl_gemv_gu_tp with the gate|up matrix [N, K] given as its 12-bit packed copy (dl_gemv_pk's format and arguments) in place of W: same bits out.
+ * bf16 only, K % 1024 == 0 (and K <= 5120 as dl_gemv_gu_tp); the packed operands are checked as dl_gemv_pk checks them. */
+int dl_gemv_gu_tp_pk(const void* data, int64_t data_bytes, const void* hdr, int64_t hdr_rows, const void* pool, int64_t pool_spans, int hb, int N, int K,
+                     const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y, const dl_tp_weights* tp, int d_model,
+                     void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base, void* granules, int call_tag, int32_t* err_flag,
+                     int dtype, int grid_cap, void* stream);
 
 /* ---- weight-streaming projection on a PRE-PACKED weight copy (round 5): the decoder's nn.Linear calls at a few hundred rows or fewer -- DML:1011-1013
  * (q|k|v), DML:1127 (o_proj), DML:328 (gate / up / down) in the post-compaction prefill layers (M = N' = 117..192) and decode steps of 4..32 rows.

@@ -73,6 +73,28 @@ for T in (226, 380):  # dl_gemv_qkv_attn: q|k|v projection + single-workgroup at
     assert int(err.item()) == 0
     plan.append({"tag": f"gemv_qkv_attn T={T}", "kernel": "gemv_qkv_attn_kernel", "N": N, "K": K, "algorithmic_bytes": N * K * 2 + 2 * T * H * 2 + 2 * H * 2})
 
+# the same launch on 12-bit packed rows (dl_gemv_qkv_attn_pk): algorithmic bytes = the packed copy (rows + headers + pool) + K/V
+from dynamic_llava_amd import bf16pack  # noqa: E402
+
+for T in (226,):
+    N, K = 3 * H, H
+    T_cap = T + 8
+    h, h2, dl = (torch.randn(1, K, device=dev, dtype=dt) for _ in range(3))
+    nw = torch.ones(K, device=dev, dtype=dt)
+    qkv, out = torch.empty(1, N, device=dev, dtype=dt), torch.empty(1, H, device=dev, dtype=dt)
+    lens = torch.tensor([T - 1], dtype=torch.int32, device=dev)
+    gran = ops.gemv_qkv_attn_workspace(nH, nH, d, dev)
+    err = torch.zeros(1, dtype=torch.int32, device=dev)
+    for rep in range(3):
+        pw = bf16pack.pack(torch.randn(N, K, device=dev, dtype=dt) * 0.02)
+        k = torch.randn(1, nH, T_cap, d, device=dev, dtype=dt)
+        v = torch.randn_like(k)
+        torch.cuda.synchronize()
+        ops.gemv_qkv_attn_pk(pw, qkv, h, h2, dl, nw, 1e-5, cos, sin, lens, lens, k, v, out, gran, rep + 1, nH, nH, d, err=err)
+        torch.cuda.synchronize()
+    assert int(err.item()) == 0
+    plan.append({"tag": f"gemv_qkv_attn_pk T={T}", "kernel": "gemv_qkv_attn_kernel", "N": N, "K": K, "algorithmic_bytes": bf16pack.packed_nbytes(pw) + 2 * T * H * 2 + 2 * H * 2})
+
 tp = TextPredictor(H, 512).to(device=dev, dtype=dt)
 N, K = 22016, H
 h, h2, dl = (torch.randn(1, K, device=dev, dtype=dt) for _ in range(3))

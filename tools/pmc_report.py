@@ -7,7 +7,7 @@ import hashlib, json, os, re, sqlite3, sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # the sources the profiled launches are compiled from: bench.py refuses a committed profile whose digests differ from the tree it runs in
-PROFILED_SOURCES = ["gemv.hip", "gemv_dot.h", "attn_decode.hip", "attn_decode_body.h", "granule.h", "tp_body.h", "dl_common.h"]
+PROFILED_SOURCES = ["gemv.hip", "gemv_pk.h", "gemv_dot.h", "attn_decode.hip", "attn_decode_body.h", "granule.h", "tp_body.h", "dl_common.h"]
 
 
 def source_digests():

@@ -1,4 +1,4 @@
-// Timeline of ONE dl_gemv_qkv_attn launch (the product's q|k|v + attention launch of a batch-1 decode layer), cold weights and K/V:
+// Timeline of ONE dl_gemv_qkv_attn launch (a fourth argument `pk`: of ONE dl_gemv_qkv_attn_pk launch, rows of 12-bit packed bf16 without escapes) (the product's q|k|v + attention launch of a batch-1 decode layer), cold weights and K/V:
 // per-workgroup wall-clock stamps (100 MHz) -> when the streaming workgroups start / end, when q arrives at the attention workgroups, when the slab keys
 // are merged, when the heads are done; next to the event time of the launch and of the plain q|k|v dl_gemv on the same weights.
 //   hipcc --offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize -DDL_QA_TIMING -I include -I dynamic_llava_amd/csrc tools/qa_timing.hip -o tools/_qa_timing
@@ -6,13 +6,22 @@
 #include "../dynamic_llava_amd/csrc/gemv.hip"
 
 #include <algorithm>
+#include <string>
 #include <vector>
 
 int main(int argc, char** argv) {
   const int T = argc > 1 ? atoi(argv[1]) : 200, nH = argc > 2 ? atoi(argv[2]) : 32, D = 128, NS = argc > 3 ? atoi(argv[3]) : 1;
   const int H = nH * D, N = 3 * H, K = H, T_cap = T + 16, NBUF = 4;
-  std::vector<void*> ws(NBUF), ks(NBUF), vs(NBUF);
+  const bool pk = argc > 4 && std::string(argv[4]) == "pk";
+  const size_t pk_bytes = (size_t)N * K * 3 / 2;
+  std::vector<void*> ws(NBUF), ks(NBUF), vs(NBUF), pd(NBUF);
+  void *pk_hdr = nullptr, *pk_pool = nullptr;  // no flagged span: every header is {0, 0}, the pool is its one mandatory span
+  if (pk) {
+    hipMalloc(&pk_hdr, (size_t)N * 8); hipMemset(pk_hdr, 0, (size_t)N * 8);
+    hipMalloc(&pk_pool, 1024); hipMemset(pk_pool, 0, 1024);
+  }
   for (int i = 0; i < NBUF; ++i) {
+    if (pk) { hipMalloc(&pd[i], pk_bytes); hipMemset(pd[i], 0x3c, pk_bytes); }
     hipMalloc(&ws[i], (size_t)N * K * 2); hipMemset(ws[i], 0x3c, (size_t)N * K * 2);
     hipMalloc(&ks[i], (size_t)nH * T_cap * D * 2); hipMemset(ks[i], 0x3c, (size_t)nH * T_cap * D * 2);
     hipMalloc(&vs[i], (size_t)nH * T_cap * D * 2); hipMemset(vs[i], 0x3c, (size_t)nH * T_cap * D * 2);
@@ -38,8 +47,10 @@ int main(int argc, char** argv) {
     hipMemsetAsync(flush, it, flush_bytes, st);
     hipStreamSynchronize(st);
     hipEventRecord(e0, st);
-    int rc = dl_gemv_qkv_attn(ws[it % NBUF], K, h, h2, dl, nw, 1e-5f, qkv, cs, sn, T_cap + 8, lens, lens, ks[it % NBUF], vs[it % NBUF], (int64_t)nH * T_cap * D, (int64_t)T_cap * D, T_cap,
-                              out, gran, it + 1, err, NS, nH, nH, D, DL_BF16, 0, st);
+    int rc = pk ? dl_gemv_qkv_attn_pk(pd[it % NBUF], (int64_t)pk_bytes, pk_hdr, N, pk_pool, 1, 56, K, h, h2, dl, nw, 1e-5f, qkv, cs, sn, T_cap + 8, lens, lens, ks[it % NBUF], vs[it % NBUF],
+                                      (int64_t)nH * T_cap * D, (int64_t)T_cap * D, T_cap, out, gran, it + 1, err, NS, nH, nH, D, DL_BF16, 0, st)
+                : dl_gemv_qkv_attn(ws[it % NBUF], K, h, h2, dl, nw, 1e-5f, qkv, cs, sn, T_cap + 8, lens, lens, ks[it % NBUF], vs[it % NBUF], (int64_t)nH * T_cap * D, (int64_t)T_cap * D, T_cap,
+                                   out, gran, it + 1, err, NS, nH, nH, D, DL_BF16, 0, st);
     hipEventRecord(e1, st);
     hipStreamSynchronize(st);
     if (rc) { printf("error: %s\n", dl_last_error()); return 1; }
@@ -87,8 +98,8 @@ int main(int argc, char** argv) {
       for (int i = 0; i <= 10; ++i) printf(" %.1f", end[std::min(end.size() - 1, end.size() * i / 10)]);
       printf("\n");
     }
-    printf("T=%d heads=%d splits=%d: launch %.2f us by events (plain q|k|v dl_gemv: %.2f) | streaming workgroups start %.2f..%.2f (median %.2f), end median %.2f, p90 %.2f, last %.2f | attention workgroups start %.2f..%.2f, q arrived %.2f..%.2f, "
-           "slab keys merged by %.2f, heads done %.2f..%.2f us\n", T, nH, NS, ms * 1e3, ms2 * 1e3, start.front(), start.back(), start[start.size() / 2], end[end.size() / 2], end[end.size() * 9 / 10], end.back(), a0, a0m, qm, q, slab, donem, done);
+    printf("%s T=%d heads=%d splits=%d: launch %.2f us by events (plain q|k|v dl_gemv: %.2f) | streaming workgroups start %.2f..%.2f (median %.2f), end median %.2f, p90 %.2f, last %.2f | attention workgroups start %.2f..%.2f, q arrived %.2f..%.2f, "
+           "slab keys merged by %.2f, heads done %.2f..%.2f us\n", pk ? "packed" : "bf16", T, nH, NS, ms * 1e3, ms2 * 1e3, start.front(), start.back(), start[start.size() / 2], end[end.size() / 2], end[end.size() * 9 / 10], end.back(), a0, a0m, qm, q, slab, donem, done);
   }
   return 0;
 }
