@@ -649,33 +649,49 @@ using namespace dl;
 
 extern "C" int64_t dl_gemv_gu_tp_workspace_bytes(int d_model) { return d_model > 0 ? (int64_t)(d_model + d_model / 2) * (int64_t)sizeof(u64_t) : 0; }
 
+// What dl_gemv_gu_tp and dl_gemv_gu_tp_pk share: the checks of the common arguments, the argument block behind the weight, the grid and the LDS size.
+// `who` is the entry that was called (pk_mat_check's convention).
+static int gu_tp_setup(const char* who, GuTpArgs& a, int& grid, size_t& smem, int N, int K, const void* h_in, void* h_out, const void* delta, const void* norm_w,
+                       float eps, void* y, const dl_tp_weights* tp, int d_model, void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base,
+                       void* granules, int call_tag, int32_t* err_flag, int grid_cap) {
+  DL_REQUIRE(h_in && norm_w && y && tp && tp_workspace && decision && pos_base && granules, "%s: NULL pointer", who);
+  DL_REQUIRE(N > 0 && N % 2 == 0 && K > 0 && d_model > 0 && d_model % 32 == 0 && K % 8 == 0 && K <= 5120, "%s: bad shape N=%d K=%d d_model=%d", who, N, K, d_model);
+  DL_REQUIRE(!delta || (h_out && h_out != h_in), "%s: h_out must be a distinct buffer when delta is given", who);
+  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "%s: call_tag / grid_cap must be >= 0", who);
+  if (grid_cap == 0) grid_cap = kGemvGridCap;
+  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = y; a.N = N; a.K = K; a.eps = eps;
+  a.w = *tp; a.tp_ws = reinterpret_cast<float*>(tp_workspace); a.logits = logits_out; a.decision = decision; a.pos_base = pos_base;
+  a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag; a.D = d_model; a.call_tag = call_tag;
+  const int side = (d_model + 7) / 8 + (d_model / 2 + 7) / 8 + 1;
+  const int groups = (N / 2 + 3) / 4;
+  if (grid_cap > 2 * side) grid_cap -= side;  // projection + predictor workgroups together stay within what is resident at once (as dl_gemv_qkv_attn): with
+                                              // 1024 + 97 the last 97 streaming workgroups ran as a second round behind the others (+9 us on the launch)
+  grid = (groups < grid_cap ? groups : grid_cap) + side;
+  smem = (size_t)K * sizeof(float);  // stage 1 stages the row in fp32; the projection needs K elements of the model dtype
+  if (smem < (size_t)2 * d_model * sizeof(float)) smem = (size_t)2 * d_model * sizeof(float);
+  return DL_OK;
+}
+
+template <typename T, bool PK, typename Args>
+static void gu_tp_launch(const Args& a, int grid, size_t smem, hipStream_t st) {
+  if (a.K / Elem<T>::kVec <= 64 * 8) hipLaunchKernelGGL((gemv_gu_tp_kernel<T, 8, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  else hipLaunchKernelGGL((gemv_gu_tp_kernel<T, 10, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+}
+
 extern "C" int dl_gemv_gu_tp(const void* W, int N, int K, const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y,
                              const dl_tp_weights* tp, int d_model, void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base,
                              void* granules, int call_tag, int32_t* err_flag, int dtype, int grid_cap, void* stream) {
-  DL_REQUIRE(W && h_in && norm_w && y && tp && tp_workspace && decision && pos_base && granules, "dl_gemv_gu_tp: NULL pointer");
-  DL_REQUIRE(N > 0 && N % 2 == 0 && K > 0 && d_model > 0 && d_model % 32 == 0 && K % 8 == 0 && K <= 5120, "dl_gemv_gu_tp: bad shape N=%d K=%d d_model=%d", N, K, d_model);
-  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_gu_tp: h_out must be a distinct buffer when delta is given");
-  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_gu_tp: call_tag / grid_cap must be >= 0");
-  if (grid_cap == 0) grid_cap = kGemvGridCap;
-  hipStream_t st = as_stream(stream);
-  int rc = DL_OK;
+  DL_REQUIRE(W, "dl_gemv_gu_tp: NULL pointer");
+  GuTpArgs a;
+  int grid;
+  size_t smem;
+  if (const int rc = gu_tp_setup("dl_gemv_gu_tp", a, grid, smem, N, K, h_in, h_out, delta, norm_w, eps, y, tp, d_model, tp_workspace, logits_out, decision, pos_base,
+                                 granules, call_tag, err_flag, grid_cap)) return rc;
+  a.W = W;
   DL_DISPATCH_DTYPE(dtype, T, {
     DL_REQUIRE(K % Elem<T>::kVec == 0, "dl_gemv_gu_tp: K must be a multiple of %d", Elem<T>::kVec);
-    GuTpArgs a;
-    a.W = W; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = y; a.N = N; a.K = K; a.eps = eps;
-    a.w = *tp; a.tp_ws = reinterpret_cast<float*>(tp_workspace); a.logits = logits_out; a.decision = decision; a.pos_base = pos_base;
-    a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag; a.D = d_model; a.call_tag = call_tag;
-    const int side = (d_model + 7) / 8 + (d_model / 2 + 7) / 8 + 1;
-    const int groups = (N / 2 + 3) / 4;
-    if (grid_cap > 2 * side) grid_cap -= side;  // projection + predictor workgroups together stay within what is resident at once (as dl_gemv_qkv_attn): with
-                                                // 1024 + 97 the last 97 streaming workgroups ran as a second round behind the others (+9 us on the launch)
-    const int grid = (groups < grid_cap ? groups : grid_cap) + side;
-    size_t smem = (size_t)K * sizeof(float);  // stage 1 stages the row in fp32; the projection needs K elements of the model dtype
-    if (smem < (size_t)2 * d_model * sizeof(float)) smem = (size_t)2 * d_model * sizeof(float);
-    if (K / Elem<T>::kVec <= 64 * 8) hipLaunchKernelGGL((gemv_gu_tp_kernel<T, 8>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-    else hipLaunchKernelGGL((gemv_gu_tp_kernel<T, 10>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+    gu_tp_launch<T, false>(a, grid, smem, as_stream(stream));
   });
-  if (rc != DL_OK) return rc;
   DL_CHECK_LAUNCH("dl_gemv_gu_tp");
   return DL_OK;
 }
@@ -684,28 +700,15 @@ extern "C" int dl_gemv_gu_tp_pk(const void* data, int64_t data_bytes, const void
                                 const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* y, const dl_tp_weights* tp, int d_model,
                                 void* tp_workspace, float* logits_out, int32_t* decision, const int32_t* pos_base, void* granules, int call_tag, int32_t* err_flag,
                                 int dtype, int grid_cap, void* stream) {
-  DL_REQUIRE(h_in && norm_w && y && tp && tp_workspace && decision && pos_base && granules, "dl_gemv_gu_tp_pk: NULL pointer");
   DL_REQUIRE(dtype == DL_BF16, "dl_gemv_gu_tp_pk: bf16 only (dtype %d)", dtype);
-  DL_REQUIRE(N > 0 && N % 2 == 0 && K > 0 && d_model > 0 && d_model % 32 == 0 && K <= 5120, "dl_gemv_gu_tp_pk: bad shape N=%d K=%d d_model=%d", N, K, d_model);
   DL_REQUIRE(K % 1024 == 0 && K <= 8192, "dl_gemv_gu_tp_pk: packed rows take K %% 1024 == 0, K <= 8192 (K=%d)", K);
-  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_gu_tp_pk: h_out must be a distinct buffer when delta is given");
-  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_gu_tp_pk: call_tag / grid_cap must be >= 0");
   GuTpPkArgs a;
+  int grid;
+  size_t smem;
+  if (const int rc = gu_tp_setup("dl_gemv_gu_tp_pk", a, grid, smem, N, K, h_in, h_out, delta, norm_w, eps, y, tp, d_model, tp_workspace, logits_out, decision, pos_base,
+                                 granules, call_tag, err_flag, grid_cap)) return rc;
   if (const int rc = pk_mat_check("dl_gemv_gu_tp_pk", a.m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, N, K)) return rc;
-  if (grid_cap == 0) grid_cap = kGemvGridCap;
-  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = y; a.N = N; a.K = K; a.eps = eps;
-  a.w = *tp; a.tp_ws = reinterpret_cast<float*>(tp_workspace); a.logits = logits_out; a.decision = decision; a.pos_base = pos_base;
-  a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag; a.D = d_model; a.call_tag = call_tag;
-  // the grid and the LDS size are dl_gemv_gu_tp's
-  const int side = (d_model + 7) / 8 + (d_model / 2 + 7) / 8 + 1;
-  const int groups = (N / 2 + 3) / 4;
-  if (grid_cap > 2 * side) grid_cap -= side;
-  const int grid = (groups < grid_cap ? groups : grid_cap) + side;
-  size_t smem = (size_t)K * sizeof(float);
-  if (smem < (size_t)2 * d_model * sizeof(float)) smem = (size_t)2 * d_model * sizeof(float);
-  hipStream_t st = as_stream(stream);
-  if (K / 8 <= 64 * 8) hipLaunchKernelGGL((gemv_gu_tp_kernel<bf16_t, 8, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-  else hipLaunchKernelGGL((gemv_gu_tp_kernel<bf16_t, 10, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  gu_tp_launch<bf16_t, true>(a, grid, smem, as_stream(stream));
   DL_CHECK_LAUNCH("dl_gemv_gu_tp_pk");
   return DL_OK;
 }
@@ -715,46 +718,61 @@ extern "C" int64_t dl_gemv_qkv_attn_workspace_bytes(int n_heads, int n_kv_heads,
   return ((int64_t)(n_heads + 2 * n_kv_heads) * head_dim + (int64_t)n_heads * (kQaMaxSplits - 1) * (head_dim + 2)) * (int64_t)sizeof(u64_t);
 }
 
+// What dl_gemv_qkv_attn and dl_gemv_qkv_attn_pk share: the checks of the common arguments, the argument block behind the weight, the grid (R: the projection's
+// rows per wave per pass, kQaR or kQaPkR).  `who` is the entry that was called (pk_mat_check's convention).
+static int qkv_attn_setup(const char* who, QkvAttnArgs& a, int& grid, int R, int K, const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps,
+                          void* qkv, const void* cos_tab, const void* sin_tab, int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab, void* v_slab,
+                          int64_t slab_stride_b, int64_t slab_stride_h, int T_cap, void* out, void* granules, int call_tag, int32_t* err_flag, int n_splits,
+                          int n_heads, int n_kv_heads, int head_dim, int grid_cap) {
+  DL_REQUIRE(h_in && norm_w && qkv && cos_tab && sin_tab && pos_base && kv_len && k_slab && v_slab && out && granules, "%s: NULL pointer", who);
+  DL_REQUIRE(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && (head_dim == 128 || head_dim == 64) && K > 0 && n_pos > 0 && T_cap > 0, "%s: bad shape", who);
+  DL_REQUIRE(!delta || (h_out && h_out != h_in), "%s: h_out must be a distinct buffer when delta is given", who);
+  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "%s: call_tag / grid_cap must be >= 0", who);
+  DL_REQUIRE(n_splits >= 1 && n_splits <= kQaMaxSplits, "%s: n_splits=%d must be in [1, %d]", who, n_splits, kQaMaxSplits);
+  if (grid_cap == 0) grid_cap = kGemvGridCap;
+  const int N = (n_heads + 2 * n_kv_heads) * head_dim;
+  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = qkv; a.N = N; a.K = K; a.eps = eps;
+  a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.pos_base = pos_base; a.kv_len = kv_len; a.k_slab = k_slab; a.v_slab = v_slab; a.out = out;
+  a.stride_b = slab_stride_b; a.stride_h = slab_stride_h; a.n_pos = n_pos; a.T_cap = T_cap; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads;
+  a.call_tag = call_tag; a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag;
+  // one workgroup per head: the whole row (speculative first request of 256 keys, as the stand-alone single-split launch); several: 128 keys
+  // each = the two trips a workgroup holds in registers while it waits for q, the last one takes what is left
+  a.n_splits = n_splits;
+  a.chunk_keys = n_splits == 1 ? 256 : 128;
+  const int n_attn = n_heads * n_splits;
+  const int groups = (N + 4 * R - 1) / (4 * R);
+  if (grid_cap > 2 * n_attn) grid_cap -= n_attn;  // projection + attention workgroups together stay within what is resident at once
+  grid = (groups < grid_cap ? groups : grid_cap) + n_attn;
+  return DL_OK;
+}
+
+// the LDS holds the K elements of the normalised row in the model dtype
+template <typename T, bool PK, typename Args>
+static void qkv_attn_launch(const Args& a, int head_dim, int grid, hipStream_t st) {
+  const size_t smem = (size_t)a.K * Elem<T>::kBytes;
+  if (a.n_splits == 1) {
+    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 128, false, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 64, false, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  } else {
+    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 128, true, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 64, true, PK>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
+  }
+}
+
 extern "C" int dl_gemv_qkv_attn(const void* W, int K, const void* h_in, void* h_out, const void* delta, const void* norm_w, float eps, void* qkv,
                                 const void* cos_tab, const void* sin_tab, int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab,
                                 void* v_slab, int64_t slab_stride_b, int64_t slab_stride_h, int T_cap, void* out, void* granules, int call_tag,
                                 int32_t* err_flag, int n_splits, int n_heads, int n_kv_heads, int head_dim, int dtype, int grid_cap, void* stream) {
-  DL_REQUIRE(W && h_in && norm_w && qkv && cos_tab && sin_tab && pos_base && kv_len && k_slab && v_slab && out && granules, "dl_gemv_qkv_attn: NULL pointer");
-  DL_REQUIRE(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && (head_dim == 128 || head_dim == 64) && K > 0 && n_pos > 0 && T_cap > 0,
-             "dl_gemv_qkv_attn: bad shape");
-  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_qkv_attn: h_out must be a distinct buffer when delta is given");
-  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_qkv_attn: call_tag / grid_cap must be >= 0");
-  DL_REQUIRE(n_splits >= 1 && n_splits <= kQaMaxSplits, "dl_gemv_qkv_attn: n_splits=%d must be in [1, %d]", n_splits, kQaMaxSplits);
-  if (grid_cap == 0) grid_cap = kGemvGridCap;
-  const int N = (n_heads + 2 * n_kv_heads) * head_dim;
-  hipStream_t st = as_stream(stream);
-  int rc = DL_OK;
+  DL_REQUIRE(W, "dl_gemv_qkv_attn: NULL pointer");
+  QkvAttnArgs a;
+  int grid;
+  if (const int rc = qkv_attn_setup("dl_gemv_qkv_attn", a, grid, kQaR, K, h_in, h_out, delta, norm_w, eps, qkv, cos_tab, sin_tab, n_pos, pos_base, kv_len, k_slab, v_slab,
+                                    slab_stride_b, slab_stride_h, T_cap, out, granules, call_tag, err_flag, n_splits, n_heads, n_kv_heads, head_dim, grid_cap)) return rc;
+  a.W = W;
   DL_DISPATCH_DTYPE(dtype, T, {
     DL_REQUIRE(K % Elem<T>::kVec == 0 && (size_t)K * Elem<T>::kBytes <= 48 * 1024, "dl_gemv_qkv_attn: K=%d unsupported", K);
-    QkvAttnArgs a;
-    a.W = W; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = qkv; a.N = N; a.K = K; a.eps = eps;
-    a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.pos_base = pos_base; a.kv_len = kv_len; a.k_slab = k_slab; a.v_slab = v_slab; a.out = out;
-    a.stride_b = slab_stride_b; a.stride_h = slab_stride_h; a.n_pos = n_pos; a.T_cap = T_cap; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads;
-    a.call_tag = call_tag; a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag;
-
-    // one workgroup per head: the whole row (speculative first request of 256 keys, as the stand-alone single-split launch); several: 128 keys
-    // each = the two trips a workgroup holds in registers while it waits for q, the last one takes what is left
-    a.n_splits = n_splits;
-    a.chunk_keys = n_splits == 1 ? 256 : 128;
-    const int n_attn = n_heads * n_splits;
-    const int groups = (N + 4 * kQaR - 1) / (4 * kQaR);
-    if (grid_cap > 2 * n_attn) grid_cap -= n_attn;  // projection + attention workgroups together stay within what is resident at once
-    const int grid = (groups < grid_cap ? groups : grid_cap) + n_attn;
-    const size_t smem = (size_t)K * Elem<T>::kBytes;
-    if (n_splits == 1) {
-      if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 128, false>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-      else hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 64, false>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-    } else {
-      if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 128, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-      else hipLaunchKernelGGL((gemv_qkv_attn_kernel<T, 64, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-    }
+    qkv_attn_launch<T, false>(a, head_dim, grid, as_stream(stream));
   });
-  if (rc != DL_OK) return rc;
   DL_CHECK_LAUNCH("dl_gemv_qkv_attn");
   return DL_OK;
 }
@@ -764,37 +782,14 @@ extern "C" int dl_gemv_qkv_attn_pk(const void* data, int64_t data_bytes, const v
                                    int n_pos, const int32_t* pos_base, const int32_t* kv_len, void* k_slab, void* v_slab, int64_t slab_stride_b, int64_t slab_stride_h,
                                    int T_cap, void* out, void* granules, int call_tag, int32_t* err_flag, int n_splits, int n_heads, int n_kv_heads, int head_dim,
                                    int dtype, int grid_cap, void* stream) {
-  DL_REQUIRE(h_in && norm_w && qkv && cos_tab && sin_tab && pos_base && kv_len && k_slab && v_slab && out && granules, "dl_gemv_qkv_attn_pk: NULL pointer");
   DL_REQUIRE(dtype == DL_BF16, "dl_gemv_qkv_attn_pk: bf16 only (dtype %d)", dtype);
-  DL_REQUIRE(n_heads > 0 && n_kv_heads > 0 && n_heads % n_kv_heads == 0 && (head_dim == 128 || head_dim == 64) && K > 0 && n_pos > 0 && T_cap > 0,
-             "dl_gemv_qkv_attn_pk: bad shape");
   DL_REQUIRE(K % 1024 == 0 && K <= 8192, "dl_gemv_qkv_attn_pk: packed rows take K %% 1024 == 0, K <= 8192 (K=%d)", K);
-  DL_REQUIRE(!delta || (h_out && h_out != h_in), "dl_gemv_qkv_attn_pk: h_out must be a distinct buffer when delta is given");
-  DL_REQUIRE(call_tag >= 0 && grid_cap >= 0, "dl_gemv_qkv_attn_pk: call_tag / grid_cap must be >= 0");
-  DL_REQUIRE(n_splits >= 1 && n_splits <= kQaMaxSplits, "dl_gemv_qkv_attn_pk: n_splits=%d must be in [1, %d]", n_splits, kQaMaxSplits);
-  const int N = (n_heads + 2 * n_kv_heads) * head_dim;
   QkvAttnPkArgs a;
-  if (const int rc = pk_mat_check("dl_gemv_qkv_attn_pk", a.m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, N, K)) return rc;
-  if (grid_cap == 0) grid_cap = kGemvGridCap;
-  a.W = nullptr; a.h = h_in; a.h_out = h_out; a.delta = delta; a.nw = norm_w; a.y = qkv; a.N = N; a.K = K; a.eps = eps;
-  a.cos_tab = cos_tab; a.sin_tab = sin_tab; a.pos_base = pos_base; a.kv_len = kv_len; a.k_slab = k_slab; a.v_slab = v_slab; a.out = out;
-  a.stride_b = slab_stride_b; a.stride_h = slab_stride_h; a.n_pos = n_pos; a.T_cap = T_cap; a.n_heads = n_heads; a.n_kv_heads = n_kv_heads;
-  a.call_tag = call_tag; a.gran = reinterpret_cast<u64_t*>(granules); a.err = err_flag;
-  a.n_splits = n_splits;  // (the attention workgroups and their key chunks: as dl_gemv_qkv_attn)
-  a.chunk_keys = n_splits == 1 ? 256 : 128;
-  const int n_attn = n_heads * n_splits;
-  const int groups = (N + 4 * kQaPkR - 1) / (4 * kQaPkR);
-  if (grid_cap > 2 * n_attn) grid_cap -= n_attn;  // projection + attention workgroups together stay within what is resident at once
-  const int grid = (groups < grid_cap ? groups : grid_cap) + n_attn;
-  const size_t smem = (size_t)K * 2;
-  hipStream_t st = as_stream(stream);
-  if (n_splits == 1) {
-    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 128, false, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 64, false, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-  } else {
-    if (head_dim == 128) hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 128, true, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-    else hipLaunchKernelGGL((gemv_qkv_attn_kernel<bf16_t, 64, true, true>), dim3((unsigned)grid), dim3(kGemvThreads), smem, st, a);
-  }
+  int grid;
+  if (const int rc = qkv_attn_setup("dl_gemv_qkv_attn_pk", a, grid, kQaPkR, K, h_in, h_out, delta, norm_w, eps, qkv, cos_tab, sin_tab, n_pos, pos_base, kv_len, k_slab, v_slab,
+                                    slab_stride_b, slab_stride_h, T_cap, out, granules, call_tag, err_flag, n_splits, n_heads, n_kv_heads, head_dim, grid_cap)) return rc;
+  if (const int rc = pk_mat_check("dl_gemv_qkv_attn_pk", a.m, data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb, a.N, K)) return rc;
+  qkv_attn_launch<bf16_t, true>(a, head_dim, grid, as_stream(stream));
   DL_CHECK_LAUNCH("dl_gemv_qkv_attn_pk");
   return DL_OK;
 }

@@ -124,119 +124,115 @@ class DecodeScheduler:
         else:
             self._decode_step_gemm(st, cache)
         if advance:
-            sc = self.config.sparse_config
-            use_tp = bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and sc["sparse_layer"] < self.config.num_hidden_layers
-            if getattr(self, "_forced", False):  # score(): the same bookkeeping around the label, scored
-                ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, cache.len_full, cache.len_sparse,
-                                 st.decision if use_tp else None)
-            elif getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
-                ops.decode_sample(
-                    st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
-                    st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
-                )
-            else:
-                ops.decode_advance(
-                    st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, cache.len_full, cache.len_sparse,
-                    st.decision if use_tp else None, min_new_tokens=getattr(self, "_min_new", 0),
-                )
+            self._bookkeep(st, cache, getattr(self, "_min_new", 0))
+
+    def _bookkeep(self, st, cache, min_new):
+        """The launch that closes a step: pick the token (argmax, a sampled one, or the label, scored), append it, set the EOS flags and advance the KV lengths
+        by the predictor's decision.  cache None: the first token -- the prompt's KV lengths are already in place, so neither they nor the decision are passed."""
+        lf, ls = (None, None) if cache is None else (cache.len_full, cache.len_sparse)
+        dec = st.decision if cache is not None and self._use_tp() else None
+        if getattr(self, "_forced", False):  # score(): the same bookkeeping around the label, scored
+            ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, lf, ls, dec)
+        elif getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
+            ops.decode_sample(st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+        else:  # EOS is banned while step < min_new (HF semantics)
+            ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+
+    def _use_tp(self):
+        """The output text predictor decides in the decode step (it sits in front of a layer that exists)."""
+        sc = self.config.sparse_config
+        return bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and sc["sparse_layer"] < self.config.num_hidden_layers
+
+    def _attn_call_tag(self, i):
+        """Layer i's call_tag for the stand-alone attention launches: >= 0 lets a split-KV launch merge its splits itself, -1 keeps the separate merge launch."""
+        return (i & 0xff) if self.attn_inkernel_combine and self.config.num_hidden_layers >= 2 else -1
+
+    def _tp_decide(self, st, h, side_stream):
+        """F6: the text predictor's decision on h, the hidden state entering layer `sparse_layer` (DML:2377-2391).  Only the end-of-step length advance consumes
+        it, so with side_stream it runs on a snapshot of h on st.tp_stream (a parallel branch of the captured graph), off the layer chain's critical
+        path; the caller joins the stream before anything reads st.decision."""
+        tp = self.model.output_text_score_predictor
+        if side_stream:
+            st.tp_x.copy_(h)
+            st.tp_stream.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(st.tp_stream):
+                tp.decide(st.tp_x, st.tp_ws, st.tp_logits, st.decision)
+        else:
+            tp.decide(h, st.tp_ws, st.tp_logits, st.decision)
+
+    def _streams_packed(self, st):
+        """Batch 1, model-dtype format: the matrices that have a 12-bit packed copy (model._pack_decode_weights) stream it -- same bits out."""
+        return self.decode_weight_pack and st.B == 1 and self.decode_weight_format is None
+
+    def _layer_streams(self, st, layer):
+        """-> what this step reads (q|k|v, o_proj, gate|up, down_proj) of `layer` from: the MXFP8 codes as a (q, scale) pair (set_decode_weight_format), the
+        bf16pack.PackedBf16 copy where one exists and applies, else the model-dtype tensor.  ops.gemv_any and the fused launches' front doors take any of them."""
+        if self.decode_weight_format == "mxfp8":
+            m = layer.mx8
+            return m["qkv"], m["o"], m["gu"], m["down"]
+        pk = (getattr(layer, "pk", None) or {}) if self._streams_packed(st) else {}
+        pk_qkv = getattr(layer, "pk_qkv", None) if self._streams_packed(st) and self.decode_weight_pack_qkv else None
+        src = lambda p, w: w if p is None else p
+        return src(pk_qkv, layer.w_qkv), src(pk.get("o"), layer.self_attn.o_proj.weight), src(pk.get("gu"), layer.w_gu), src(pk.get("down"), layer.mlp.down_proj.weight)
+
+    def _lm_head_stream(self, st):
+        """The vocabulary projection's source, chosen as _layer_streams chooses (it has no MXFP8 codes)."""
+        p = getattr(self, "_pk_lm_head", None) if self._streams_packed(st) else None
+        return self.lm_head.weight if p is None else p
 
     def _decode_step_gemv(self, st: _DecodeState, cache: KVSlabCache):
-        """Small-batch decode step: 5 weight-streaming launches per layer (dl_gemv with fused residual-add+RMSNorm /
-        SiLU*up prologues) + RoPE/KV append + split-KV attention.  The residual stream ping-pongs between st.h / st.h2."""
-        cfg, sc = self.config, self.config.sparse_config
+        """Small-batch decode step: 5 weight-streaming launches per layer (GEMVs with fused residual-add+RMSNorm / SiLU*up prologues) + RoPE/KV append +
+        split-KV attention.  One launch order for every weight storage (_layer_streams); per projection the step decides only whether the launch is the
+        fused one.  The residual stream ping-pongs between st.h / st.h2."""
+        cfg = self.config
         nH, nKV, d = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
-        eps, L, SL = cfg.rms_norm_eps, cfg.num_hidden_layers, sc["sparse_layer"]
+        eps, SL = cfg.rms_norm_eps, cfg.sparse_config["sparse_layer"]
         cos, sin = self._rope
-        use_tp = bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and SL < L
+        use_tp = self._use_tp()
         torch.index_select(self.model.embed_tokens.weight, 0, st.cur_ids, out=st.h)
         h_cur, h_alt, delta = st.h, st.h2, None
         A = ops.GEMV_ADDNORM
-        # MXFP8 decoder weights (set_decode_weight_format): the four projections stream (q, scale) on dl_gemv_mx8; the two fused model-dtype launches
-        # (dl_gemv_qkv_attn, dl_gemv_gu_tp) are not used -- the unfused sequence runs instead (stand-alone attention, the predictor's decide)
+        # MXFP8 decoder weights are a storage the two fused launches (dl_gemv_qkv_attn, dl_gemv_gu_tp) do not take: the unfused sequence runs instead (stand-alone
+        # attention, the predictor's decide).  gu_grid_cap sizes the model-dtype and the packed gate|up launch only: dl_gemv_mx8 runs its default grid
         mx8 = self.decode_weight_format == "mxfp8"
-        # batch 1, model-dtype format: the matrices that have a 12-bit packed copy (model._pack_decode_weights) stream it on dl_gemv_pk -- same bits out
-        pack = self.decode_weight_pack and st.B == 1 and self.decode_weight_format is None
-        no_pk = {"o": None, "gu": None, "down": None}
+        gu_grid = {} if mx8 else {"grid_cap": self.gu_grid_cap}
         for i, layer in enumerate(self.model.layers):
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
-            pk = (getattr(layer, "pk", None) or no_pk) if pack else no_pk
-            pk_qkv = getattr(layer, "pk_qkv", None) if pack and self.decode_weight_pack_qkv else None
-            if mx8:
-                self._decode_layer_mx8(st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp)
-                if delta is not None:
-                    h_cur, h_alt = h_alt, h_cur
-                h_cur, h_alt = h_alt, h_cur
-                delta = st.dn
-                continue
+            w_qkv, w_o, w_gu, w_down = self._layer_streams(st, layer)
             # q|k|v projection + single-split attention of a batch-1 layer in ONE launch (dl_gemv_qkv_attn: the attention workgroups fetch their
             # K/V rows while the weights stream and receive the projection as granules).  Same bodies as the two launches below, so the
             # results are bit-identical to them WHEN the stand-alone attention also runs four waves (KVSlabCache.eight_wave_single_split =
             # False, as the kernel tests set it); by default the stand-alone single-split launch of a small batch runs eight waves -- another
             # (equally valid) summation order, so DL_FUSE_QKV_ATTN=0 is an A/B of speed, not of bits (tokens / KV lengths: tested equal)
-            fused_attn = self.fuse_qkv_attn and st.B == 1 and ns == 1 and st.qa_gran is not None and cache.kv_format is None
-            if fused_attn and pk_qkv is not None:
-                ops.gemv_qkv_attn_pk(pk_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
-                                     st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
-                                     n_splits=cache.fused_attn_splits(i, self.fused_attn_max_splits))
-                if delta is not None:
-                    h_cur, h_alt = h_alt, h_cur
-            elif fused_attn:
-                ops.gemv_qkv_attn(layer.w_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
-                                  st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
-                                  n_splits=cache.fused_attn_splits(i, self.fused_attn_max_splits))
-                if delta is not None:
-                    h_cur, h_alt = h_alt, h_cur
-            elif pk_qkv is not None:
-                ops.gemv_pk(pk_qkv, st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
-                if delta is not None:
-                    h_cur, h_alt = h_alt, h_cur
+            fused_attn = self.fuse_qkv_attn and st.B == 1 and ns == 1 and st.qa_gran is not None and cache.kv_format is None and not mx8
+            if fused_attn:
+                ops.gemv_qkv_attn_any(w_qkv, st.qkv, h_cur, h_alt, delta, layer.input_layernorm.weight, eps, cos, sin, cache.len_full, lens, cache.k[i], cache.v[i],
+                                      st.attn, st.qa_gran, i & 0xff, nH, nKV, d, err=st.blk_err, grid_cap=self.qkv_attn_grid_cap,
+                                      n_splits=cache.fused_attn_splits(i, self.fused_attn_max_splits))
             else:
-                ops.gemv(layer.w_qkv, st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
-                if delta is not None:
-                    h_cur, h_alt = h_alt, h_cur
+                ops.gemv_any(w_qkv, st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
+            if delta is not None:
+                h_cur, h_alt = h_alt, h_cur
             # the predictor as extra workgroups of this layer's gate|up launch (dl_gemv_gu_tp): its input is that launch's h_in
-            fused_tp = i == SL and use_tp and self.fuse_gu_tp and not self.tp_side_stream and st.B == 1 and st.tp_gran is not None
-            if i == SL and use_tp and not fused_tp:  # F6: decision on the hidden state entering layer SL (DML:2377-2391)
-                # only the end-of-step length advance consumes the decision: run the predictor on a side stream (a parallel
-                # branch of the captured graph) on a snapshot of the residual stream, off the layer chain's critical path
-                if self.tp_side_stream:
-                    st.tp_x.copy_(h_cur)
-                    st.tp_stream.wait_stream(torch.cuda.current_stream())
-                    with torch.cuda.stream(st.tp_stream):
-                        self.model.output_text_score_predictor.decide(st.tp_x, st.tp_ws, st.tp_logits, st.decision)
-                else:
-                    self.model.output_text_score_predictor.decide(h_cur, st.tp_ws, st.tp_logits, st.decision)
+            fused_tp = i == SL and use_tp and self.fuse_gu_tp and not self.tp_side_stream and st.B == 1 and st.tp_gran is not None and not mx8
+            if i == SL and use_tp and not fused_tp:
+                self._tp_decide(st, h_cur, self.tp_side_stream)
             # F8+F10+F9: RoPE, KV append at slot len[b] and ragged attention in one launch (1024-thread workgroups; split-KV
             # only when the row is long enough to need more than one workgroup per head)
             if not fused_attn:
-                self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
-            if pk["o"] is not None:
-                ops.gemv_pk(pk["o"], st.o, x=st.attn)
-            else:
-                ops.gemv(layer.self_attn.o_proj.weight, st.o, x=st.attn)
-            if fused_tp and pk["gu"] is not None:
+                self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, self._attn_call_tag(i))
+            ops.gemv_any(w_o, st.o, x=st.attn)
+            if fused_tp:
                 tp = self.model.output_text_score_predictor
-                ops.gemv_gu_tp_pk(pk["gu"], st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
-                                  st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
-            elif fused_tp:
-                tp = self.model.output_text_score_predictor
-                ops.gemv_gu_tp(layer.w_gu, st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
-                               st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
-            elif pk["gu"] is not None:
-                ops.gemv_pk(pk["gu"], st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps, grid_cap=self.gu_grid_cap)
+                ops.gemv_gu_tp_any(w_gu, st.gu, h_cur, h_alt, st.o, layer.post_attention_layernorm.weight, eps, tp._weights(), tp.d_model, st.tp_ws, st.tp_logits,
+                                   st.decision, cache.len_full, st.tp_gran, i & 0xff, err=st.blk_err)
             else:
-                ops.gemv(layer.w_gu, st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps, grid_cap=self.gu_grid_cap)
+                ops.gemv_any(w_gu, st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps, **gu_grid)
             h_cur, h_alt = h_alt, h_cur
-            if pk["down"] is not None:
-                ops.gemv_pk(pk["down"], st.dn, x=st.gu)
-            else:
-                ops.gemv(layer.mlp.down_proj.weight, st.dn, x=st.gu)
+            ops.gemv_any(w_down, st.dn, x=st.gu)
             delta = st.dn
-        if pack and getattr(self, "_pk_lm_head", None) is not None:
-            ops.gemv_pk(self._pk_lm_head, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
-        else:
-            ops.gemv(self.lm_head.weight, st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
+        ops.gemv_any(self._lm_head_stream(st), st.logits, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=self.model.norm.weight, eps=eps)
         if use_tp and self.tp_side_stream:
             torch.cuda.current_stream().wait_stream(st.tp_stream)  # join before anything reads st.decision
 
@@ -266,31 +262,6 @@ class DecodeScheduler:
         cls = KVSlabCacheMX8 if self.kv_cache_format == "mxfp8" else KVSlabCache
         return cls(cfg.num_hidden_layers, cfg.sparse_config["sparse_layer"], B, cfg.num_key_value_heads, cfg.head_dim, int(t_cap), self.dtype, self.device)
 
-    def _decode_layer_mx8(self, st, cache, i, layer, h_cur, h_alt, delta, lens, ns, use_tp):
-        """One layer of _decode_step_gemv on MXFP8 weights: the unfused launch sequence of the model-dtype step with dl_gemv_mx8 in place of dl_gemv.
-        The residual stream ping-pongs exactly as there (the caller swaps h_cur / h_alt)."""
-        cfg, sc = self.config, self.config.sparse_config
-        nH, nKV, d, eps = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim, cfg.rms_norm_eps
-        cos, sin = self._rope
-        A = ops.GEMV_ADDNORM
-        m = layer.mx8
-        ops.gemv_mx8(*m["qkv"], st.qkv, mode=A, h_in=h_cur, h_out=h_alt, delta=delta, norm_w=layer.input_layernorm.weight, eps=eps)
-        if delta is not None:
-            h_cur, h_alt = h_alt, h_cur
-        if i == sc["sparse_layer"] and use_tp:  # F6: decision on the hidden state entering layer SL (DML:2377-2391)
-            if self.tp_side_stream:
-                st.tp_x.copy_(h_cur)
-                st.tp_stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(st.tp_stream):
-                    self.model.output_text_score_predictor.decide(st.tp_x, st.tp_ws, st.tp_logits, st.decision)
-            else:
-                self.model.output_text_score_predictor.decide(h_cur, st.tp_ws, st.tp_logits, st.decision)
-        L = cfg.num_hidden_layers
-        self._attn_decode_rope(st, cache, i, st.qkv, lens, ns, (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1)
-        ops.gemv_mx8(*m["o"], st.o, x=st.attn)
-        ops.gemv_mx8(*m["gu"], st.gu, mode=A | ops.GEMV_OUT_SILU_PAIR, h_in=h_cur, h_out=h_alt, delta=st.o, norm_w=layer.post_attention_layernorm.weight, eps=eps)
-        ops.gemv_mx8(*m["down"], st.dn, x=st.gu)
-
     def _decode_step_gemm(self, st: _DecodeState, cache: KVSlabCache):
         """Decode step for batches past the GEMV range (round 5, `profiles/r05_decode_batch_paths.txt`).  Up to smallm_max_decode_batch (32) rows:
         o_proj -- and q|k|v below packed_decode_qkv_min_batch (16) rows -- on dl_gemm_smallm (row-major weights streamed into the matrix cores, fp32
@@ -302,7 +273,7 @@ class DecodeScheduler:
         nH, nKV, d = cfg.num_attention_heads, cfg.num_key_value_heads, cfg.head_dim
         eps, L, SL = cfg.rms_norm_eps, cfg.num_hidden_layers, sc["sparse_layer"]
         cos, sin = self._rope
-        use_tp = bool(sc["use_text_predictor"] and sc["use_output_text_predictor"]) and SL < L
+        use_tp = self._use_tp()
         sm, ws = st.use_smallm, st.lin_ws
         torch.index_select(self.model.embed_tokens.weight, 0, st.cur_ids, out=st.h)
         lp_qkv = st.use_lp_mlp and st.B >= self.packed_decode_qkv_min_batch and getattr(self.model.layers[0], "wp_qkv", None) is not None
@@ -312,11 +283,11 @@ class DecodeScheduler:
             qkv_parts = self.packed_decode_qkv_parts and st.B <= self.packed_decode_qkv_parts_max_batch and ks_q == 2 and self.dtype in (torch.bfloat16, torch.float16)
         ops.rmsnorm(st.h, self.model.layers[0].input_layernorm.weight, eps, out=st.x_pk if lp_qkv else st.x, packed=lp_qkv)
         for i, layer in enumerate(self.model.layers):
-            if i == SL and use_tp:  # F6: decision on the hidden state entering layer SL (DML:2377-2391)
-                self.model.output_text_score_predictor.decide(st.h, st.tp_ws, st.tp_logits, st.decision)
+            if i == SL and use_tp:
+                self._tp_decide(st, st.h, False)  # (this step keeps the predictor on the layer chain)
             lens = cache.len_of_layer(i)
             ns = cache.n_splits(i, st.B * nH)
-            tag = (i & 0xff) if self.attn_inkernel_combine and L >= 2 else -1
+            tag = self._attn_call_tag(i)
             if st.use_mx8_gemm:
                 self._decode_layer_gemm_mx8(st, cache, i, layer, lens, ns, tag)
                 continue
@@ -493,10 +464,4 @@ class DecodeScheduler:
         else:
             torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
         self._prefill_logits_buf.copy_(st.logits)
-        # first token: argmax only (the prompt's KV lengths are already in place); EOS is banned while step < min_new (HF semantics)
-        if getattr(self, "_forced", False):  # label 0 is scored on the prompt's last logits
-            ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, None, None, None)
-        elif getattr(self, "_sampled", False):  # token 0 is drawn with step = 0
-            ops.decode_sample(st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)
-        else:
-            ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, None, None, None, min_new_tokens=min_new)
+        self._bookkeep(st, None, min_new)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits

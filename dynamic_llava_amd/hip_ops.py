@@ -12,6 +12,8 @@ from ctypes import POINTER, Structure, c_char_p, c_float, c_int, c_int32, c_int6
 
 import torch
 
+from .bf16pack import PackedBf16
+
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "libdynllava_hip.so")
 
@@ -631,22 +633,23 @@ def gemv_max_batch(K, dtype):
     return int(lib().dl_gemv_max_batch(int(K), dtype_code(dtype)))
 
 
+def _gemv_x_stride(mode, x, h_in, h_out, delta, B, K):
+    """gemv() / gemv_mx8(): checks the prologue's inputs for y [B, .] and w [., K]; -> x's row stride as the entries take it (0 with GEMV_ADDNORM, which reads h_in)."""
+    if (mode & 3) == GEMV_ADDNORM:
+        assert h_in.is_contiguous() and h_in.shape == (B, K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
+        return 0
+    assert x.stride(1) == 1 and x.shape[0] == B
+    return x.stride(0)
+
+
 def gemv(w, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_w=None, eps=0.0, grid_cap=0):
     """y[b,:] = W @ prologue(x)[b,:] (see include/dynllava.h).  w [N,K]; y [B,N] (row stride y.stride(0))."""
     _dev(w, y, x, h_in, h_out, delta, norm_w)
     assert w.is_contiguous() and y.stride(1) == 1
     N, K = w.shape
     B = y.shape[0]
-    if (mode & 3) == GEMV_ADDNORM:
-        assert h_in.is_contiguous() and h_in.shape == (B, K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
-        xs = 0
-    else:
-        assert x.stride(1) == 1 and x.shape[0] == B
-        xs = x.stride(0)
-    _check(
-        lib().dl_gemv(mode, _p(w), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(w.dtype), int(grid_cap), _stream()),
-        "dl_gemv",
-    )
+    xs = _gemv_x_stride(mode, x, h_in, h_out, delta, B, K)
+    _check(lib().dl_gemv(mode, _p(w), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(w.dtype), int(grid_cap), _stream()), "dl_gemv")
     return y
 
 
@@ -659,18 +662,13 @@ def gemv_pk_ok(mode, K, dtype):
 
 def gemv_pk(p, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=None, norm_w=None, eps=0.0, grid_cap=0):
     """gemv() at batch 1 on a losslessly packed bf16 weight (p: bf16pack.PackedBf16 of w [N,K]): bit-identical to gemv(w, ...), 0.75-0.8 of the bytes."""
-    _dev(p.data, p.hdr, p.pool, y, x, h_in, h_out, delta, norm_w)
-    assert p.data.dtype == torch.uint8 and p.pool.dtype == torch.uint8 and p.hdr.dtype == torch.int32 and p.data.is_contiguous() and p.hdr.is_contiguous() and p.pool.is_contiguous()
+    _dev(y, x, h_in, h_out, delta, norm_w)
     assert y.dtype == torch.bfloat16 and y.shape[0] == 1 and y.stride(1) == 1
     if (mode & 3) == GEMV_ADDNORM:
         assert h_in.is_contiguous() and h_in.shape == (1, p.K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
     else:
         assert x.stride(1) == 1 and x.shape[0] == 1 and x.shape[1] >= p.K
-    _check(
-        lib().dl_gemv_pk(mode, _p(p.data), p.data.numel(), _p(p.hdr), p.hdr.shape[0], _p(p.pool), p.pool.numel() // 1024, int(p.hb), p.N, p.K, _p(x), _p(h_in), _p(h_out),
-                         _p(delta), _p(norm_w), eps, _p(y), 1, dtype_code(y.dtype), int(grid_cap), _stream()),
-        "dl_gemv_pk",
-    )
+    _check(lib().dl_gemv_pk(mode, *_pk_args(p), p.N, p.K, _p(x), _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), 1, dtype_code(y.dtype), int(grid_cap), _stream()), "dl_gemv_pk")
     return y
 
 
@@ -703,18 +701,22 @@ def gemv_mx8(q, scale, y, x=None, mode=GEMV_PLAIN, h_in=None, h_out=None, delta=
     N, K = q.shape
     assert scale.shape == (N, K // 32)
     B = y.shape[0]
-    if (mode & 3) == GEMV_ADDNORM:
-        assert h_in.is_contiguous() and h_in.shape == (B, K) and (delta is None or (delta.is_contiguous() and h_out.is_contiguous()))
-        xs = 0
-    else:
-        assert x.stride(1) == 1 and x.shape[0] == B
-        xs = x.stride(0)
-    _check(
-        lib().dl_gemv_mx8(mode, _p(q), _p(scale), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(y.dtype),
-                          int(grid_cap), _stream()),
-        "dl_gemv_mx8",
-    )
+    xs = _gemv_x_stride(mode, x, h_in, h_out, delta, B, K)
+    _check(lib().dl_gemv_mx8(mode, _p(q), _p(scale), N, K, _p(x), xs, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), y.stride(0), B, dtype_code(y.dtype),
+                             int(grid_cap), _stream()), "dl_gemv_mx8")
     return y
+
+
+def _wrapper_for(w, tensor, packed):
+    """The wrapper that takes the storage `w` is held in -- a tensor or a bf16pack.PackedBf16 -- looked up by name at call time (tests spy on the wrappers)."""
+    if not isinstance(w, (torch.Tensor, PackedBf16)):
+        raise TypeError(f"{tensor} / {packed}: the weight is a tensor or a PackedBf16, not {type(w).__name__}")
+    return globals()[tensor if isinstance(w, torch.Tensor) else packed]
+
+
+def gemv_any(w, y, **kw):
+    """gemv() on the storage `w` is held in: a tensor (gemv), a bf16pack.PackedBf16 (gemv_pk) or the (q, scale) pair of its MXFP8 codes (gemv_mx8)."""
+    return gemv_mx8(*w, y, **kw) if isinstance(w, tuple) and len(w) == 2 else _wrapper_for(w, "gemv", "gemv_pk")(w, y, **kw)
 
 
 MX8_PLAIN, MX8_PARTS = 0, 1  # dl_gemm_mx8's epilogues (include/dynllava.h)
@@ -770,53 +772,48 @@ def gemv_qkv_attn_workspace(n_heads, n_kv_heads, head_dim, device):
     return torch.zeros(n // 8, dtype=torch.int64, device=device)
 
 
-def gemv_qkv_attn(w, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim,
-                  err=None, grid_cap=0, n_splits=1):
-    """One launch = gemv(w, qkv, mode=GEMV_ADDNORM, ...) + attn_decode_rope(qkv, ..., n_splits=1) for ONE row (see include/dynllava.h).
-    n_splits: attention workgroups per head (1..4; > 1: 128 slab keys each, partials merged by the head's first workgroup)."""
-    _dev(w, qkv, h_in, h_out, delta, norm_w, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, err)
-    N, K = w.shape
-    assert w.is_contiguous() and qkv.shape == (1, N) and qkv.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
+def _pk_args(p):
+    """(data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb) of a bf16pack.PackedBf16, as dl_gemv_pk and the fused packed launches take them."""
+    _dev(p.data, p.hdr, p.pool)
+    assert p.data.dtype == torch.uint8 and p.pool.dtype == torch.uint8 and p.hdr.dtype == torch.int32 and p.data.is_contiguous() and p.hdr.is_contiguous() and p.pool.is_contiguous()
+    return _p(p.data), p.data.numel(), _p(p.hdr), p.hdr.shape[0], _p(p.pool), p.pool.numel() // 1024, int(p.hb)
+
+
+def _qkv_attn_args(N, K, dtype, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim, err, grid_cap, n_splits):
+    """The checks and the argument list behind the weight that dl_gemv_qkv_attn and dl_gemv_qkv_attn_pk share (w [N, K] of `dtype`)."""
+    _dev(qkv, h_in, h_out, delta, norm_w, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, err)
+    assert qkv.shape == (1, N) and qkv.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
     assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
     assert out.shape == (1, n_heads * head_dim) and out.is_contiguous() and N == (n_heads + 2 * n_kv_heads) * head_dim
     assert pos_base.dtype == torch.int32 and kv_len.dtype == torch.int32 and granules.numel() * granules.element_size() >= lib().dl_gemv_qkv_attn_workspace_bytes(int(n_heads), int(n_kv_heads), int(head_dim))
     assert k_slab.stride(3) == 1 and k_slab.stride(2) == head_dim and k_slab.stride() == v_slab.stride()
-    sb, sh = k_slab.stride(0), k_slab.stride(1)
-    _check(
-        lib().dl_gemv_qkv_attn(
-            _p(w), K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(qkv), _p(cos), _p(sin), cos.shape[0], _p(pos_base), _p(kv_len), _p(k_slab), _p(v_slab), sb, sh,
-            k_slab.shape[2], _p(out), _p(granules), int(call_tag), _p(err), int(n_splits), int(n_heads), int(n_kv_heads), int(head_dim), dtype_code(w.dtype), int(grid_cap), _stream(),
-        ),
-        "dl_gemv_qkv_attn",
-    )
+    return (K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(qkv), _p(cos), _p(sin), cos.shape[0], _p(pos_base), _p(kv_len), _p(k_slab), _p(v_slab), k_slab.stride(0), k_slab.stride(1),
+            k_slab.shape[2], _p(out), _p(granules), int(call_tag), _p(err), int(n_splits), int(n_heads), int(n_kv_heads), int(head_dim), dtype_code(dtype), int(grid_cap), _stream())
+
+
+def gemv_qkv_attn(w, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim,
+                  err=None, grid_cap=0, n_splits=1):
+    """One launch = gemv(w, qkv, mode=GEMV_ADDNORM, ...) + attn_decode_rope(qkv, ..., n_splits=1) for ONE row (see include/dynllava.h).
+    n_splits: attention workgroups per head (1..4; > 1: 128 slab keys each, partials merged by the head's first workgroup)."""
+    _dev(w)
+    assert w.is_contiguous()
+    tail = _qkv_attn_args(*w.shape, w.dtype, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim, err, grid_cap, n_splits)
+    _check(lib().dl_gemv_qkv_attn(_p(w), *tail), "dl_gemv_qkv_attn")
     return out
-
-
-def _pk_args(p):
-    """(data, data_bytes, hdr, hdr_rows, pool, pool_spans, hb) of a bf16pack.PackedBf16, as dl_gemv_pk and the fused packed launches take them."""
-    assert p.data.dtype == torch.uint8 and p.pool.dtype == torch.uint8 and p.hdr.dtype == torch.int32 and p.data.is_contiguous() and p.hdr.is_contiguous() and p.pool.is_contiguous()
-    return _p(p.data), p.data.numel(), _p(p.hdr), p.hdr.shape[0], _p(p.pool), p.pool.numel() // 1024, int(p.hb)
 
 
 def gemv_qkv_attn_pk(p, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim,
                      err=None, grid_cap=0, n_splits=1):
     """gemv_qkv_attn() on a losslessly packed q|k|v matrix (p: bf16pack.PackedBf16 of w [N,K]): bit-identical outputs, 0.79 of the weight bytes."""
-    _dev(p.data, p.hdr, p.pool, qkv, h_in, h_out, delta, norm_w, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, err)
-    N, K = p.N, p.K
-    assert qkv.dtype == torch.bfloat16 and qkv.shape == (1, N) and qkv.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
-    assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
-    assert out.shape == (1, n_heads * head_dim) and out.is_contiguous() and N == (n_heads + 2 * n_kv_heads) * head_dim
-    assert pos_base.dtype == torch.int32 and kv_len.dtype == torch.int32 and granules.numel() * granules.element_size() >= lib().dl_gemv_qkv_attn_workspace_bytes(int(n_heads), int(n_kv_heads), int(head_dim))
-    assert k_slab.stride(3) == 1 and k_slab.stride(2) == head_dim and k_slab.stride() == v_slab.stride()
-    sb, sh = k_slab.stride(0), k_slab.stride(1)
-    _check(
-        lib().dl_gemv_qkv_attn_pk(
-            *_pk_args(p), K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(qkv), _p(cos), _p(sin), cos.shape[0], _p(pos_base), _p(kv_len), _p(k_slab), _p(v_slab), sb, sh,
-            k_slab.shape[2], _p(out), _p(granules), int(call_tag), _p(err), int(n_splits), int(n_heads), int(n_kv_heads), int(head_dim), dtype_code(qkv.dtype), int(grid_cap), _stream(),
-        ),
-        "dl_gemv_qkv_attn_pk",
-    )
+    assert qkv.dtype == torch.bfloat16
+    tail = _qkv_attn_args(p.N, p.K, qkv.dtype, qkv, h_in, h_out, delta, norm_w, eps, cos, sin, pos_base, kv_len, k_slab, v_slab, out, granules, call_tag, n_heads, n_kv_heads, head_dim, err, grid_cap, n_splits)
+    _check(lib().dl_gemv_qkv_attn_pk(*_pk_args(p), *tail), "dl_gemv_qkv_attn_pk")
     return out
+
+
+def gemv_qkv_attn_any(w, *args, **kw):
+    """gemv_qkv_attn() on a tensor, gemv_qkv_attn_pk() on a bf16pack.PackedBf16; the fused launch does not take MXFP8 codes (TypeError)."""
+    return _wrapper_for(w, "gemv_qkv_attn", "gemv_qkv_attn_pk")(w, *args, **kw)
 
 
 def gemv_gu_tp_workspace(d_model, device):
@@ -824,36 +821,37 @@ def gemv_gu_tp_workspace(d_model, device):
     return torch.zeros(int(lib().dl_gemv_gu_tp_workspace_bytes(int(d_model))) // 8, dtype=torch.int64, device=device)
 
 
-def gemv_gu_tp(w, y, h_in, h_out, delta, norm_w, eps, tp_weights: TpWeights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err=None, grid_cap=0):
-    """One launch = gemv(w, y, mode=GEMV_ADDNORM | GEMV_OUT_SILU_PAIR, ...) + text_predictor_decide(h_in, ...) for ONE row (see include/dynllava.h)."""
-    _dev(w, y, h_in, h_out, delta, norm_w, tp_workspace, logits_out, decision, pos_base, granules, err)
-    N, K = w.shape
-    assert w.is_contiguous() and y.shape == (1, N // 2) and y.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
+def _gu_tp_args(N, K, dtype, y, h_in, h_out, delta, norm_w, eps, tp_weights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err, grid_cap):
+    """The checks and the argument list behind the weight that dl_gemv_gu_tp and dl_gemv_gu_tp_pk share (w [N, K] of `dtype`)."""
+    _dev(y, h_in, h_out, delta, norm_w, tp_workspace, logits_out, decision, pos_base, granules, err)
+    assert y.shape == (1, N // 2) and y.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
     assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
     assert decision.dtype == torch.int32 and pos_base.dtype == torch.int32 and tp_workspace.dtype == torch.float32
     assert tp_workspace.numel() * 4 >= lib().dl_text_predictor_workspace_bytes(1, d_model) and granules.numel() * granules.element_size() >= lib().dl_gemv_gu_tp_workspace_bytes(d_model)
-    _check(
-        lib().dl_gemv_gu_tp(_p(w), N, K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), ctypes.byref(tp_weights), int(d_model), _p(tp_workspace), _p(logits_out),
-                            _p(decision), _p(pos_base), _p(granules), int(call_tag), _p(err), dtype_code(w.dtype), int(grid_cap), _stream()),
-        "dl_gemv_gu_tp",
-    )
+    return (N, K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), ctypes.byref(tp_weights), int(d_model), _p(tp_workspace), _p(logits_out),
+            _p(decision), _p(pos_base), _p(granules), int(call_tag), _p(err), dtype_code(dtype), int(grid_cap), _stream())
+
+
+def gemv_gu_tp(w, y, h_in, h_out, delta, norm_w, eps, tp_weights: TpWeights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err=None, grid_cap=0):
+    """One launch = gemv(w, y, mode=GEMV_ADDNORM | GEMV_OUT_SILU_PAIR, ...) + text_predictor_decide(h_in, ...) for ONE row (see include/dynllava.h)."""
+    _dev(w)
+    assert w.is_contiguous()
+    tail = _gu_tp_args(*w.shape, w.dtype, y, h_in, h_out, delta, norm_w, eps, tp_weights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err, grid_cap)
+    _check(lib().dl_gemv_gu_tp(_p(w), *tail), "dl_gemv_gu_tp")
     return y
 
 
 def gemv_gu_tp_pk(p, y, h_in, h_out, delta, norm_w, eps, tp_weights: TpWeights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err=None, grid_cap=0):
     """gemv_gu_tp() on a losslessly packed gate|up matrix (p: bf16pack.PackedBf16 of w [N,K]): bit-identical outputs."""
-    _dev(p.data, p.hdr, p.pool, y, h_in, h_out, delta, norm_w, tp_workspace, logits_out, decision, pos_base, granules, err)
-    N, K = p.N, p.K
-    assert y.dtype == torch.bfloat16 and y.shape == (1, N // 2) and y.is_contiguous() and h_in.is_contiguous() and h_in.shape == (1, K)
-    assert delta is None or (delta.is_contiguous() and h_out.is_contiguous())
-    assert decision.dtype == torch.int32 and pos_base.dtype == torch.int32 and tp_workspace.dtype == torch.float32
-    assert tp_workspace.numel() * 4 >= lib().dl_text_predictor_workspace_bytes(1, d_model) and granules.numel() * granules.element_size() >= lib().dl_gemv_gu_tp_workspace_bytes(d_model)
-    _check(
-        lib().dl_gemv_gu_tp_pk(*_pk_args(p), N, K, _p(h_in), _p(h_out), _p(delta), _p(norm_w), eps, _p(y), ctypes.byref(tp_weights), int(d_model), _p(tp_workspace), _p(logits_out),
-                               _p(decision), _p(pos_base), _p(granules), int(call_tag), _p(err), dtype_code(y.dtype), int(grid_cap), _stream()),
-        "dl_gemv_gu_tp_pk",
-    )
+    assert y.dtype == torch.bfloat16
+    tail = _gu_tp_args(p.N, p.K, y.dtype, y, h_in, h_out, delta, norm_w, eps, tp_weights, d_model, tp_workspace, logits_out, decision, pos_base, granules, call_tag, err, grid_cap)
+    _check(lib().dl_gemv_gu_tp_pk(*_pk_args(p), *tail), "dl_gemv_gu_tp_pk")
     return y
+
+
+def gemv_gu_tp_any(w, *args, **kw):
+    """gemv_gu_tp() on a tensor, gemv_gu_tp_pk() on a bf16pack.PackedBf16; the fused launch does not take MXFP8 codes (TypeError)."""
+    return _wrapper_for(w, "gemv_gu_tp", "gemv_gu_tp_pk")(w, *args, **kw)
 
 
 def decode_advance(logits, next_ids, out_ids=None, step=None, finished=None, eos_id=-1, pad_id=0, kv_len_full=None, kv_len_sparse=None, decision=None, min_new_tokens=0):

@@ -484,8 +484,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             if st.tp_gran is not None:
                 st.tp_gran.zero_()
             self._decode_step_kernels(st, cache, False)
-            sc_ = self.config.sparse_config
-            use_tp = bool(sc_["use_text_predictor"] and sc_["use_output_text_predictor"]) and sc_["sparse_layer"] < self.config.num_hidden_layers
+            use_tp = self._use_tp()
             cache.lens[0] += 1
             dec_ = st.decision if use_tp else 1
             if use_tp and self.force_text_decision is not None:
