@@ -512,12 +512,14 @@ def linear(a, w, bias=None, flags=0, residual=None, out=None):
     return out
 
 
-def layernorm(x, w, b, eps=1e-5, row_index=None, rows=None):
-    _dev(x, w, b, row_index)
+def layernorm(x, w, b, eps=1e-5, row_index=None, rows=None, out=None):
+    _dev(x, w, b, row_index, out)
     assert x.is_contiguous()
     H = x.shape[-1]
     rows = (x.numel() // H) if rows is None else rows
-    out = torch.empty((rows, H), dtype=x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((rows, H), dtype=x.dtype, device=x.device)
+    assert out.is_contiguous() and out.dtype == x.dtype and out.numel() == rows * H
     _check(lib().dl_layernorm(_p(x), _p(row_index), _p(w), _p(b), _p(out), rows, H, eps, dtype_code(x.dtype), _stream()), "dl_layernorm")
     return out
 

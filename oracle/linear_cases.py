@@ -608,20 +608,20 @@ def all_instantiations():
 
 
 def omitted():
-    """instantiation -> the one-line reason it has no entry."""
-    out = {}
-    for B in range(1, 9):
-        for pro in (1, 2):
-            out[f"gemv_kernel<f32,{B},{pro},plain,2,4>"] = "fp32 prologue: rsqrt(1 + eps) and silu(16) are not lattice values in fp32; held by test_gemv_modes' tolerance"
-        for pro in (0, 1, 2):
-            out[f"gemv_kernel<f32,{B},{pro},pair,2,4>"] = "fp32 SiLU-pair epilogue: silu(16) != 16 in fp32; held by test_gemv_modes' tolerance"
-        out[f"gemv_mx8_kernel<f32,{B},1,plain,2,4>"] = "fp32 ADDNORM prologue: as dl_gemv's; held by tests/test_mxfp8_gpu.py"
-        out[f"gemv_mx8_kernel<f32,{B},1,pair,2,4>"] = "fp32 ADDNORM prologue + SiLU-pair epilogue: as dl_gemv's; held by tests/test_mxfp8_gpu.py"
-    for dt in HALF:
-        for s in LT_SHAPES:
-            for epi in ("QGELU", "GELU"):
-                out[lt_inst(dt, s, 0).replace("BIAS", epi)] = "GELU / QuickGELU epilogue: transcendental, out of scope; held by tests/test_linear_tiles_gpu.py"
-    return out
+    """instantiation -> the one-line reason it has no entry.  Empty: the fp32 prologues and SiLU-pair epilogues of dl_gemv / dl_gemv_mx8 (their results are
+    no lattice values) and the GELU / QuickGELU epilogues of dl_linear_tiles are driven by oracle/rowwise_cases.py under its feasible-set criterion."""
+    return {}
+
+
+def driven():
+    """Every instantiation of all_instantiations() that a table drives: the tables below, and those of oracle/rowwise_cases.py that reach this family."""
+    from oracle import rowwise_cases as rc
+
+    out = set()
+    for table, _ in TABLES.values():
+        for e in table:
+            out |= e["inst"]
+    return out | (rc.driven() & all_instantiations())
 
 
 TABLES = {
