@@ -14,7 +14,10 @@
 //   dV_j = sum_i A_ij dO_i = sum_i (pe_ij / Dn_i) dO_i + (eps/N) * sum_i dO_i / Dn_i
 //   dS_ij = dE_ij * pe_ij;  dQ_i = scale * sum_j dS_ij k_j;  dK_j = scale * sum_i dS_ij q_i
 //   dpolicy_j = sum_h sum_{i != j} dE_ij * exp(s_ij - m_i)
-// (the gradient through max_j -- O(eps) because softmax is shift invariant up to the eps terms -- is not propagated.)
+// (the gradient through max_j is not propagated.  Softmax is shift invariant up to the eps terms, so that gradient is O(eps / Dn_i):
+//    sum_j dS_ij = (eps * delta_i - (eps/N) * dO_i . sum_j v_j) / Dn_i
+//  -- negligible while Dn_i >= 1 (the row's maximum is a kept key or its own), of the order of the gradient itself in a row whose
+//  maximum is a dropped key far above every kept one (Dn_i -> eps).  Measured per input in docs/train_policy_error_budget.md.)
 //
 // Kernels: MFMA 16x16x32 flash-style tiles, 64 query rows x 64 keys, 4 waves.  The backward is two deterministic passes (no atomics):
 // one workgroup per KEY tile accumulates dK / dV / dpolicy over the query tiles, one per QUERY tile accumulates dQ over the key tiles.
@@ -697,16 +700,20 @@ static int tp_fwd_go(const void* q, const void* k, const void* v, TpStrides qs, 
   return go(std::integral_constant<int, 4>{});
 }
 
+// waves per workgroup of the two backward kernels (16 keys / 16 query rows each, sharing one staged tile of the other side): 8 at
+// head_dim 128 once the launch still has >= 256 workgroups (two waves per SIMD where four leave one: L=2048 1160 -> 685 us), else 4
+// (head_dim 64 already fits two 4-wave workgroups per CU; short rows need the workgroup count: L=631 187 vs 229 us)
+static int tp_bwd_waves(int B, int H, int L, int head_dim) {
+  return head_dim == 128 && (int64_t)B * H * ((L + 127) / 128) >= 256 ? 8 : 4;
+}
+
 template <typename T, int D, bool CAUSAL>
 static int tp_bwd_go(const void* q, const void* k, const void* v, TpStrides qs, const void* o, const void* d_o, void* dq, void* dk, void* dv, TpStrides os,
                      const float* policy, const void* bias, int64_t bias_sb, int64_t bias_sl, const float* M, const float* Dn, float* delta, float* gsum,
                      float* dpol_heads, int B, int H, int L, float scale, float c_leak, hipStream_t st) {
   hipLaunchKernelGGL((tp_delta_kernel<T>), dim3((unsigned)((L + 3) / 4), (unsigned)H, (unsigned)B), dim3(256), 0, st, o, d_o, os, delta, H, L, D);
   hipLaunchKernelGGL((tp_colsum_kernel<T>), dim3((unsigned)H, (unsigned)B), dim3(256), 0, st, d_o, os, Dn, gsum, H, L, D);
-  // waves per workgroup of the two backward kernels (16 keys / 16 query rows each, sharing one staged tile of the other side): 8 at
-  // head_dim 128 once the launch still has >= 256 workgroups (two waves per SIMD where four leave one: L=2048 1160 -> 685 us), else 4
-  // (head_dim 64 already fits two 4-wave workgroups per CU; short rows need the workgroup count: L=631 187 vs 229 us)
-  const bool wide = D == 128 && (int64_t)B * H * ((L + 127) / 128) >= 256;
+  const bool wide = tp_bwd_waves(B, H, L, D) == 8;
   auto go = [&](auto nw_tag) -> int {
     constexpr int NW = decltype(nw_tag)::value;
     const dim3 grid((unsigned)((L + NW * 16 - 1) / (NW * 16)), (unsigned)H, (unsigned)B);
@@ -757,6 +764,11 @@ static bool tp_common_ok(const char* who, int B, int H, int L, int head_dim, int
 extern "C" int64_t dl_attn_policy_workspace_floats(int B, int H, int L, int head_dim) {
   // forward: sumv [B,H,d]; backward: delta [B,H,L] + gsum [B,H,d]
   return (int64_t)B * H * (L + 2 * (int64_t)head_dim);
+}
+
+extern "C" int dl_attn_policy_bwd_waves(int B, int H, int L, int head_dim) {
+  if (!(B > 0 && H > 0 && L > 0 && (head_dim == 64 || head_dim == 128))) return 0;
+  return tp_bwd_waves(B, H, L, head_dim);
 }
 
 extern "C" int dl_attn_policy_fwd(const void* q, const void* k, const void* v, const int64_t* qkv_strides, void* out, const int64_t* o_strides,

@@ -122,6 +122,7 @@ SIGNATURES = {
     "dl_gemv_gu_tp_pk": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_void_p, POINTER(TpWeights),
                                  c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p]),
     "dl_attn_policy_workspace_floats": (c_int64, [c_int, c_int, c_int, c_int]),
+    "dl_attn_policy_bwd_waves": (c_int, [c_int, c_int, c_int, c_int]),
     "dl_attn_policy_fwd": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p,
                                    c_int, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_void_p]),
     "dl_attn_policy_bwd": (c_int, [c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, POINTER(c_int64), c_void_p, c_void_p, c_int64, c_int64,
@@ -954,6 +955,11 @@ def _strides3(t):
 
 def attn_policy_workspace(B, H, L, d, device):
     return torch.empty(int(lib().dl_attn_policy_workspace_floats(B, H, L, d)), device=device, dtype=torch.float32)
+
+
+def attn_policy_bwd_waves(B, H, L, d):
+    """Waves per workgroup (4 or 8) of the backward kernels attn_policy_bwd launches for this shape."""
+    return int(lib().dl_attn_policy_bwd_waves(B, H, L, d))
 
 
 def _bias_args(bias, B, L):

@@ -474,9 +474,12 @@ int dl_silu_mul_parts(const float* parts, int n_slices, void* out, int64_t rows,
  * row_max / row_denom: fp32 [B,H,L] saved by the forward for the backward.  n_for_eps: the N of eps / N (the padded key count).
  * workspace: dl_attn_policy_workspace_floats(B, H, L, d) floats, the same buffer for both calls.
  * dpolicy_heads: fp32 [B,H,L]; dpolicy[b,j] = sum_h dpolicy_heads[b,h,j] (summed by the caller: deterministic, no atomics).
- * bf16 / f16, head_dim 64 or 128; dropout_p must be 0 (attention_dropout = 0.0 in every shipped config).  The O(eps) gradient through
- * max_j is not propagated. */
+ * bf16 / f16, head_dim 64 or 128; dropout_p must be 0 (attention_dropout = 0.0 in every shipped config).  The O(eps / Dn_i) gradient
+ * through max_j is not propagated (docs/train_policy_error_budget.md).
+ * dl_attn_policy_bwd_waves: waves per workgroup (4 or 8) of the two backward kernels that dl_attn_policy_bwd launches for this shape;
+ * 0 for a shape it refuses. */
 int64_t dl_attn_policy_workspace_floats(int B, int H, int L, int head_dim);
+int dl_attn_policy_bwd_waves(int B, int H, int L, int head_dim);
 int dl_attn_policy_fwd(const void* q, const void* k, const void* v, const int64_t* qkv_strides, void* out, const int64_t* o_strides,
                        const float* policy, const void* bias, int64_t bias_stride_b, int64_t bias_stride_row, float* row_max,
                        float* row_denom, float* workspace, int B, int H, int L, int head_dim, int causal, float scale, float eps,
