@@ -294,7 +294,7 @@ extern "C" int64_t dl_text_predictor_workspace_bytes(int B, int d_model) {
 extern "C" int dl_text_predictor_decide(const void* x, int64_t x_row_stride, int B, int H, int d_model, const dl_tp_weights* w,
                                         void* workspace, float* logits_out, int32_t* decision, int dtype, void* stream) {
   DL_REQUIRE(x && w && workspace && decision, "dl_text_predictor_decide: NULL pointer");
-  DL_REQUIRE(B > 0 && H > 0 && d_model > 0 && d_model % 32 == 0 && H % 8 == 0, "dl_text_predictor_decide: bad shape");
+  DL_REQUIRE(B > 0 && H > 0 && d_model > 0 && d_model % 32 == 0, "dl_text_predictor_decide: bad shape");  // (H: a whole number of 16-byte vectors, below)
   DL_REQUIRE(H <= 12288, "dl_text_predictor_decide: H=%d too large for LDS staging", H);
   hipStream_t st = as_stream(stream);
   float* h1 = reinterpret_cast<float*>(workspace);

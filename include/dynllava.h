@@ -270,7 +270,9 @@ int dl_vision_predictor(const void* hidden, const int32_t* cu_seqlens, const int
  * x [B,H] (hidden state entering layer `sparse_layer`); logits_out [B,2] float (may be NULL);
  * decision[b] = logit0 > logit1 (strict, raw logits).  workspace: dl_text_predictor_workspace_bytes(B, d_model)
  * (1.5*B*d_model floats).  Three launches: LN + Linear(H -> d) over d/8 workgroups, Linear(d -> d/2) over d/16 workgroups, the
- * d/2 -> d/4 -> 2 tail in one workgroup per row. */
+ * d/2 -> d/4 -> 2 tail in one workgroup per row.
+ * Shapes: H and x_row_stride are whole numbers of 16-byte vectors (multiples of 8 elements in bf16 / fp16, of 4 in fp32), H <= 12288 (the row is staged
+ * in LDS as fp32), d_model % 32 == 0; anything else is DL_ERR_ARG and nothing is launched. */
 typedef struct dl_tp_weights {
   const void *ln_w, *ln_b, *l1_w, *l1_b, *l3_w, *l3_b, *l5_w, *l5_b, *l7_w, *l7_b; /* output_mlp.0/1/3/5/7 */
 } dl_tp_weights;
@@ -389,7 +391,10 @@ int dl_prompt_layout(const int64_t* input_ids, int B, int W, int n_feat, int ima
  * logits: [B,V] in `logits_dtype` (DL_F32 or the model dtype).  step/finished: int32[B].  All state lives on
  * the device; out_ids / step / finished / kv_len_* / decision may be NULL to skip that piece of bookkeeping.
  * eos_id (-1: none), eos_id2, eos_id3 (-1: unused): the EOS set (HF accepts a list of ids).
- * min_new_tokens > 0: the EOS ids are excluded from the argmax while step[b] < min_new_tokens (HF MinNewTokensLengthLogitsProcessor). */
+ * min_new_tokens > 0: the EOS ids are excluded from the argmax while step[b] < min_new_tokens (HF MinNewTokensLengthLogitsProcessor).
+ * NaN: a NaN logit compares false with everything and is never selected; the argmax runs over the indices that are neither banned nor NaN
+ * (-inf is an ordinary value: a row of -inf yields index 0).  A row with no such index -- all NaN, or every index banned -- yields token 0.
+ * step[b] >= out_cap: out_ids is not written, everything else advances as usual. */
 int dl_decode_advance(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
                       int64_t* next_ids, int64_t* out_ids, int out_cap, int32_t* step, int32_t* finished,
                       int eos_id, int eos_id2, int eos_id3, int pad_id, int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision,
