@@ -2,7 +2,9 @@
 from __future__ import annotations
 
 
+import contextlib
 import copy
+import gc
 import math
 import os
 from dataclasses import dataclass
@@ -83,6 +85,12 @@ class _DecodeState:
         self.labels = torch.full(self.out_ids.shape, -100, dtype=torch.int64, device=device)
         self.nll = torch.zeros(self.out_ids.shape, dtype=torch.float32, device=device)
         self.top1 = torch.full(self.out_ids.shape, -1, dtype=torch.int64, device=device)
+        # dl_logits_process (generate(repetition_penalty= / no_repeat_ngram_size= / bad_words_ids=)): its fp32 output, which the bookkeeping launch then reads in the place
+        # of `logits`, its parameter block and its bad-word table -- device memory the captured launches read, rewritten by generate() before the first launch of
+        # a processed request, like sample_params: one graph serves every setting
+        self.proc_logits = torch.empty((B, V), dtype=torch.float32, device=device)
+        self.logits_params = ops.logits_params_block(device)
+        self.bad_words = ops.bad_words_table((), device)
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
         self.tp_gran = ops.gemv_gu_tp_workspace(tpm.d_model, device) if (B == 1 and tpm is not None and dtype in (torch.bfloat16, torch.float16) and H <= 5120 and H % 8 == 0 and tpm.d_model % 32 == 0) else None
@@ -94,6 +102,22 @@ class _DecodeState:
         self.obs_host = torch.empty((4, 3 * B), dtype=torch.int32).pin_memory()
         self.obs_ev = [torch.cuda.Event() for _ in range(4)]
         self.n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+
+
+@contextlib.contextmanager
+def no_gc_during_capture():
+    """Keeps Python's cyclic garbage collector from running while a stream is being captured.  A collection that starts in the middle of a capture can free a dead
+    object cycle that owns device resources -- an abandoned model with its captured graphs, streams and pinned host buffers (a prefill entry's `run` closure
+    makes a model such a cycle) -- and their destructors call runtime functions that are not permitted while any stream captures: the process aborts.
+    torch.cuda.graph() of current torch no longer collects before it begins (only with torch.compiler.config.force_cudagraph_gc).  Whatever is dead is
+    collected after the capture, at a time when freeing is legal."""
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 class DecodeScheduler:
@@ -131,12 +155,17 @@ class DecodeScheduler:
         by the predictor's decision.  cache None: the first token -- the prompt's KV lengths are already in place, so neither they nor the decision are passed."""
         lf, ls = (None, None) if cache is None else (cache.len_full, cache.len_sparse)
         dec = st.decision if cache is not None and self._use_tp() else None
+        logits = st.logits
+        if getattr(self, "_processed", False):  # generate() with logits processors: they edit the step's logits on the row's own history (HF's order: before the selection rule)
+            if getattr(self, "_forced", False):
+                raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
+            logits = ops.logits_process(st.logits, st.proc_logits, st.logits_params, st.out_ids, st.step, st.bad_words)
         if getattr(self, "_forced", False):  # score(): the same bookkeeping around the label, scored
             ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, lf, ls, dec)
         elif getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
-            ops.decode_sample(st.logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+            ops.decode_sample(logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
         else:  # EOS is banned while step < min_new (HF semantics)
-            ops.decode_advance(st.logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+            ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
 
     def _use_tp(self):
         """The output text predictor decides in the decode step (it sits in front of a layer that exists)."""
@@ -420,7 +449,7 @@ class DecodeScheduler:
             warm()
         torch.cuda.current_stream().wait_stream(s)
         g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
+        with no_gc_during_capture(), torch.cuda.graph(g):
             out = fn()
         return g, out
 
@@ -436,7 +465,8 @@ class DecodeScheduler:
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
                self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
-               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured; the sampling parameters and the labels are device data, not part of the key)
+               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)),
+               bool(getattr(self, "_processed", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured, and whether dl_logits_process runs in front of it; the sampling parameters, the labels and the processors' settings are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)

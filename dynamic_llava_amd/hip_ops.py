@@ -169,6 +169,7 @@ SIGNATURES = {
         c_int,
         [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
+    "dl_logits_process": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -946,6 +947,62 @@ def decode_score(logits, next_ids, labels, nll, top1=None, out_ids=None, step=No
         "dl_decode_score",
     )
     return next_ids
+
+
+def logits_params_words(repetition_penalty=1.0, no_repeat_ngram_size=0, n_bad_words=0):
+    """dl_logits_params (include/dynllava.h) as a CPU int32 [8] tensor: copy it into the device block (`logits_params_block`) before the first launch of
+    a request.  Values as logits_rules.normalize leaves them (penalty 1.0 = off, n-gram 0 = off)."""
+    import struct
+
+    raw = struct.pack("<fiiiiiii", float(repetition_penalty), int(no_repeat_ngram_size), int(n_bad_words), 0, 0, 0, 0, 0)
+    return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone()
+
+
+def logits_params_block(device):
+    """Device memory for one dl_logits_params (zeroed = everything off: write it with `block.copy_(logits_params_words(...))`)."""
+    return torch.zeros(8, dtype=torch.int32, device=device)
+
+
+def bad_words_table(words, device):
+    """dl_logits_process's bad-word table: int32 [MAX_BAD_WORDS, 1 + MAX_BAD_WORD_LEN] on `device`, row w = (length, ids...), unused rows zero.  words: a
+    sequence of non-empty id sequences within the device caps (logits_rules.Rules.device_route)."""
+    from .logits_rules import MAX_BAD_WORD_LEN, MAX_BAD_WORDS
+
+    words = [[int(t) for t in w] for w in (words or ())]
+    if len(words) > MAX_BAD_WORDS or any(not 1 <= len(w) <= MAX_BAD_WORD_LEN for w in words):
+        raise ValueError(f"dl_logits_process takes up to {MAX_BAD_WORDS} bad words of 1..{MAX_BAD_WORD_LEN} ids")
+    tab = torch.zeros((MAX_BAD_WORDS, 1 + MAX_BAD_WORD_LEN), dtype=torch.int32)
+    for i, w in enumerate(words):
+        tab[i, 0] = len(w)
+        tab[i, 1 : 1 + len(w)] = torch.tensor(w, dtype=torch.int32)
+    return tab.to(device)
+
+
+def logits_process(logits, out, params, out_ids=None, step=None, bad_words=None):
+    """The logits processors of one step (include/dynllava.h, logits_rules.py): logits [B, V] (any row stride) -> out fp32 [B, V], contiguous.  params: int32 [8]
+    DEVICE tensor holding a dl_logits_params; out_ids int64 [B, out_cap] + step int32 [B]: the rows' histories (None: empty); bad_words: the DEVICE table of
+    `bad_words_table` (None: no words)."""
+    _dev(logits, out, params, out_ids, step, bad_words)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    assert out.dtype == torch.float32 and out.shape == (B, V) and out.is_contiguous()
+    if params is not None:  # (None reaches the library, which refuses it)
+        assert params.dtype == torch.int32 and params.numel() >= 8 and params.is_contiguous()
+    out_cap = 0
+    if out_ids is not None:
+        assert out_ids.dtype == torch.int64 and out_ids.dim() == 2 and out_ids.shape[0] == B and out_ids.is_contiguous()
+        out_cap = out_ids.shape[1]
+    if step is not None:
+        assert step.dtype == torch.int32 and step.numel() == B and step.is_contiguous()
+    if bad_words is not None:
+        from .logits_rules import MAX_BAD_WORD_LEN, MAX_BAD_WORDS
+
+        assert bad_words.dtype == torch.int32 and bad_words.shape == (MAX_BAD_WORDS, 1 + MAX_BAD_WORD_LEN) and bad_words.is_contiguous()
+    _check(
+        lib().dl_logits_process(_p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(out), _p(out_ids), out_cap, _p(step), _p(params), _p(bad_words), _stream()),
+        "dl_logits_process",
+    )
+    return out
 
 
 def _strides3(t):

@@ -33,11 +33,11 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import sampling, scoring
+from . import logits_rules, sampling, scoring
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
-from .decode import DecodeScheduler, _DecodeState  # noqa: F401
+from .decode import DecodeScheduler, _DecodeState, no_gc_during_capture  # noqa: F401
 from .modules import (CLIPVisionTower, CausalLMOutputWithPast, DynamicLlamaDecoderLayer, DynamicLlavaLlamaModel, TextPredictor,  # noqa: F401 (re-exported:
                       VisionPredictor)  # tests, tools and the package's lazy attributes import these names from here)
 from .prefill import USER_IDS, PrefillEngine  # noqa: F401
@@ -414,6 +414,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "clip_tiles_ksplit": [getattr(self.get_vision_tower(), "tiles_ksplit_out", None), getattr(self.get_vision_tower(), "tiles_ksplit_fc2", None)],
             "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch, "kv_cache_format": self.kv_cache_format,
             "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
+            "device_logits_processors": True,  # repetition_penalty / no_repeat_ngram_size / bad_words_ids act inside the captured graphs (dl_logits_process)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }
@@ -539,13 +540,22 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         min_new = int(kwargs.get("min_new_tokens", 0) or 0)
         return int(max_new), min(min_new, int(max_new)), eos, (0 if pad is None else int(pad))
 
+    def _logits_rules(self, kwargs):
+        """The request's logits processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids), validated: logits_rules.Rules.  The EOS set is resolved as
+        _gen_kwargs resolves it (a one-token bad word equal to an EOS id is dropped, as in HF)."""
+        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
+        eos_set = [] if eos is None else ([int(e) for e in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
+        return logits_rules.normalize(kwargs, self.config.vocab_size, eos_set)
+
     @torch.no_grad()
     def _generate_sample(self, inputs, images, greedy=False, **kwargs):
         """`greedy=True` (round 4): the same plain loop over forward() taking the argmax -- the route for requests the device-side greedy loop does not
         take (more than three EOS ids: dl_decode_advance compares three).  do_sample=True: temperature / top_k / top_p sampling as HF's logits warpers define them (TemperatureLogitsWarper,
         TopKLogitsWarper, TopPLogitsWarper: the smallest set of most probable tokens whose mass reaches top_p is kept), drawn with
         torch's generator -- a plain loop over forward() (no hipGraph: this is the convenience path, the harness default is greedy).
-        Token streams cannot match HF's draw for draw (different RNG consumption); the distribution per step is the same."""
+        Token streams cannot match HF's draw for draw (different RNG consumption); the distribution per step is the same.
+        repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call."""
+        rules = self._logits_rules(kwargs)
         temperature = float(kwargs.get("temperature", 1.0) or 1.0)
         top_k = int(kwargs.get("top_k", 0) or 0)
         top_p = kwargs.get("top_p")
@@ -563,7 +573,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         finished = torch.zeros(B, dtype=torch.bool, device=self.device)
         toks, scores = [], []
         for step in range(max_new):
-            z = logits.float() / temperature
+            z = logits.float()
+            if rules.on:
+                z = rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
+            z = z / temperature
             if step < min_new and eos_set:
                 z[:, eos_set] = float("-inf")
             if top_k > 0:
@@ -603,7 +616,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         the image placeholder of the first turn the reference's `input_ids[:, past_length:]` slicing (DML:2831-2853) has no consistent meaning,
         and its own multi-round harness drives forward() (model_lvis_multi_round_for_ppl.py:108-220).  The new chunk goes through the
         chunk-on-cache path (DML:2506-2521: the instruct predictor decides which of its K/V rows stay in layers >= sparse_layer), the new
-        tokens through single decode steps; plain loop over forward(), no hipGraph."""
+        tokens through single decode steps; plain loop over forward(), no hipGraph.  repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process
+        on every step's logits, on the tokens emitted in this call."""
+        rules = self._logits_rules(kwargs)
         if images is not None or kwargs.get("image_features") is not None:
             raise NotImplementedError("generate(past_key_values=...) continues a dialogue: the image belongs to the first call")
         cache = kwargs["past_key_values"]
@@ -631,7 +646,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         finished = torch.zeros(inputs.shape[0], dtype=torch.bool, device=self.device)
         toks, scores = [], []
         for step in range(max_new):
-            z = logits.clone()
+            z = rules.apply(logits, torch.stack(toks, dim=1) if toks else [[]] * inputs.shape[0]) if rules.on else logits.clone()
             if step < min_new and eos_set:
                 z[:, eos_set] = float("-inf")
             scores.append(z)
@@ -693,11 +708,20 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         with seed=<int> on the device, inside the same captured graphs as greedy decoding (dl_decode_sample; the rule is sampling.py;
         sample_row_base=<int> offsets the rows' random streams for sharded batches); without seed, or with generator=, through
         _generate_sample on torch's RNG), num_beams(1), use_cache(True), eos_token_id, pad_token_id, attention_mask,
-        return_dict_in_generate (+ output_scores), image_features (pre-computed projector output, testing).
+        return_dict_in_generate (+ output_scores), image_features (pre-computed projector output, testing),
+        repetition_penalty / no_repeat_ngram_size / bad_words_ids (HF's RepetitionPenalty / NoRepeatNGram / NoBadWords logits processors, bit for bit, on the
+        tokens generated in this call -- the prompt is never part of the history, as for HF driven by inputs_embeds; on the device inside the same captured
+        graphs (dl_logits_process; the rule is logits_rules.py), in front of the EOS ban of min_new_tokens and of temperature / top_k / top_p; a request past
+        logits_rules.MAX_NGRAM / MAX_BAD_WORDS / MAX_BAD_WORD_LEN runs the plain loop over forward() with the same rule; `scores` are the processed logits,
+        `logits` the raw ones).  Bad values of these raise ValueError before any launch.
+        Still ignored without a word: streamer, stopping_criteria, logits_processor, suppress_tokens, sequence_bias.
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
         the new token ids / pixels into static buffers."""
         self._check_ready()
+        rules = self._logits_rules(kwargs)  # validated here, before any launch
+        if rules.on and kwargs.get("_score_labels") is not None:
+            raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
         sampled = None  # (temperature, top_k, top_p, seed, row base) when the device sampler draws the tokens
         if kwargs.get("do_sample", False):  # model_vqa_loader.py:162-175 passes do_sample = temperature > 0 (default 0: greedy)
             if "inputs_embeds" in kwargs:
@@ -709,6 +733,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             sampled = sampling.normalize_params(kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p")) + (int(kwargs["seed"]), int(kwargs.get("sample_row_base", 0) or 0))
         if kwargs.get("past_key_values") is not None:
             return self._generate_on_cache(inputs, images, **kwargs)
+        if rules.on and not rules.device_route:
+            # past the device caps (logits_rules.MAX_*): the plain loop over forward(), which applies the same rule on the host -- sampled (torch's RNG) or greedy
+            if kwargs.get("do_sample", False):
+                return self._generate_sample(inputs, images, **kwargs)
+            return self._generate_sample(inputs, images, greedy=True, **{k: v for k, v in kwargs.items() if k not in ("do_sample", "sync_every")})
         attention_mask = kwargs.get("attention_mask")
         image_features = kwargs.get("image_features")
         sync_every = int(kwargs.get("sync_every", self.decode_sync_every))  # decode steps enqueued between two observations of the device state
@@ -766,6 +795,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._sampled = sampled is not None  # which bookkeeping kernel _first_token / the decode steps launch (and capture)
         if sampled is not None:
             st.sample_params.copy_(ops.sample_params_words(*sampled))
+        self._processed = rules.on  # dl_logits_process in front of the bookkeeping kernel (launched, and captured); an all-neutral request is exactly the request without the keywords
+        if rules.on:  # the settings are device data like the sampling parameters: one graph serves every penalty, n-gram size and word list
+            st.logits_params.copy_(ops.logits_params_words(rules.repetition_penalty, rules.no_repeat_ngram_size, len(rules.bad_words)))
+            st.bad_words.copy_(ops.bad_words_table(rules.bad_words, "cpu"))
         forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
         self._forced = forced is not None  # dl_decode_score in the place of dl_decode_advance: score the label, feed the label
         if forced is not None:
@@ -785,7 +818,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
             key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
                    cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._eos, self._pad, min_new, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled, self._forced)  # (a knob toggled at run time must not replay a graph captured under the other setting)
+                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled, self._forced, self._processed)  # (a knob toggled at run time must not replay a graph captured under the other setting)
             ent = self._prefill_graphs.get(key)
             if ent is None:
                 # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
@@ -841,7 +874,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                         # (the allocator drops a private pool with its last graph: a handle whose graphs are all gone must not be reused)
                         self._prefill_pool = torch.cuda.graph_pool_handle()
                     g_ = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g_, pool=self._prefill_pool):
+                    with no_gc_during_capture(), torch.cuda.graph(g_, pool=self._prefill_pool):
                         ent["run"]()
                     ent["graph"] = g_
                     ent["run"] = None
@@ -871,6 +904,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
             if want_logits:
                 raw_logits.append(z.clone())
+            if self._processed:  # what dl_logits_process left for this step's bookkeeping launch (the buffer is read after every step on this route)
+                z = st.proc_logits.clone()
             if sampled is not None:  # the processed logits of a sampled step: z = logit / T with -inf outside the kept set (sampling.py), as HF reports them
                 # (on the host side of the loop, with the contract's own arithmetic: this branch reads the step buffer after every step anyway)
                 scores.append(sampling.processed_logits(z.cpu(), sampled[0], sampled[1], sampled[2], eos_ids if step_idx < min_new else ()).to(z.device))

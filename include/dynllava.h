@@ -449,6 +449,38 @@ int dl_decode_score(const void* logits, int logits_dtype, int64_t logits_row_str
                     int64_t* next_ids, int64_t* out_ids, int out_cap, int32_t* step, int32_t* finished, int pad_id,
                     int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision, void* stream);
 
+/* ---- logits processors of a decode step: repetition penalty, no-repeat n-gram and bad-word bans, the stage HF's generate() runs in front of the
+ * selection rule (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, in that order).  Runs between the lm_head
+ * launch and dl_decode_advance / dl_decode_sample, which take `out` (DL_F32) in place of the step's logits.
+ * The rule, per row (dynamic_llava_amd/logits_rules.py states it in full and is what the kernel is tested against), with g = the row's history
+ * out_ids[b, 0 : min(step[b], out_cap)] (empty when step or out_ids is NULL) and s = len(g):
+ *   1. x_v = float32(logit_v); y = x.
+ *   2. repetition_penalty p > 0, p != 1: for every token t in g, y_t = x_t * p if x_t < 0, else x_t / p -- one fp32 operation on the input logit, the
+ *      division correctly rounded.  A token that occurs several times is penalised once; -0.0 and +0.0 are divided; -inf stays -inf.
+ *   3. no_repeat_ngram n >= 1, when s + 1 >= n: with pre = the last n - 1 tokens of g, every i in [0, s - n] with g[i : i + n - 1] == pre gives
+ *      y[g[i + n - 1]] = -inf.
+ *   4. bad words: a word of length 1 bans its id at every step; a longer word w bans w[len - 1] when len <= s (HF skips a word longer than the
+ *      history) and the last len - 1 tokens of g equal w[0 : len - 1].
+ *   5. bans win over the penalty.
+ * Finished rows are processed like any other (their history then holds pad ids).  An id in the history or in the table outside [0, V) is never used
+ * as an index.  params and bad_words: DEVICE memory (one captured graph serves every setting; the host rewrites them between requests).
+ * bad_words: int32 [DL_LOGITS_MAX_BAD_WORDS][1 + DL_LOGITS_MAX_BAD_WORD_LEN], a length then the ids; rows past n_bad_words are not read; NULL: none.
+ * The kernel takes any n; DL_LOGITS_MAX_NGRAM is the limit up to which generate() sends a request here.
+ * logits: bf16 / fp16 / fp32; out: float [B, V], contiguous.  No workspace, no atomics, never synchronises: capturable.
+ * DL_ERR_ARG for a bad dtype, V < 1, B < 1 (or > 65535), a NULL logits / out / params. */
+#define DL_LOGITS_MAX_NGRAM 16
+#define DL_LOGITS_MAX_BAD_WORDS 64
+#define DL_LOGITS_MAX_BAD_WORD_LEN 8
+typedef struct dl_logits_params {
+  float repetition_penalty; /* <= 0 or 1: off */
+  int32_t no_repeat_ngram;  /* <= 0: off */
+  int32_t n_bad_words;
+  int32_t reserved[5];
+} dl_logits_params;
+int dl_logits_process(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
+                      float* out, const int64_t* out_ids, int out_cap, const int32_t* step,
+                      const dl_logits_params* params, const int32_t* bad_words, void* stream);
+
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
  * operand registers).  bf16 / f16, fp32 accumulate, one rounding.  K % 256 == 0, N % 4 == 0; ldx / ldy: row strides (elements).
