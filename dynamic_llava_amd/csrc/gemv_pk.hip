@@ -71,65 +71,107 @@ __global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(WP
   }
 }
 
-// ---- plain prologue, long rows (down_proj; 8192 < K <= 16384): gemv_b1_plain_halves_kernel on packed rows.  A row is shared by the two waves of a
-// pair -- the row's two segments -- and the even wave adds the partial sums low half first.  RW rows per pair and pass. ----
-template <int C, int RW, int WPE, int TF>
-__global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(WPE, WPE))) void gemv_pk_halves_kernel(PkMat m, int N, int K, const void* __restrict__ x_,
-                                                                                                              void* __restrict__ y_) {
-  static_assert(C % 2 == 0, "whole slots");
-  constexpr int SLOTS = C / 2;
-  __shared__ float part[RW][kGemvThreads / 64];
-  const int lane = threadIdx.x & 63, wid = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (a scalar: row addresses stay in SGPRs)
+// ---- plain prologue, long rows (down_proj; 8192 < K <= 16384), x in LDS: gemv_b1_plain_halves_kernel on packed rows at four workgroups per CU.  A row is
+// shared by the two waves of a pair -- the row's two segments, split at the bf16 kernel's hv -- and the even wave adds the partial sums low half first.
+// The workgroup stages x once as two zero-padded segment images of C chunk slots per lane each (image `half`: chunks [v0, v1) of x, then zeros: a read
+// past the low half's end must not land on the high half's x), AFTER it has requested its first pass and headers, so that the staging shares the first
+// weights' round trip.  A wave walks its segment in passes of SLOTS pairs inside a RUNTIME loop (when it is unrolled, the compiler hoists the LDS reads of x
+// into registers and spills) with two pass buffers: the next pass of the rows is requested before the current one is dotted.  It dots all C chunk slots, the
+// padded ones too, as the bf16 kernel does (a padded chunk adds +0, which is not nothing for a -0 accumulator).  R rows per pair and pass. ----
+template <int R, int SLOTS>
+__global__ __launch_bounds__(kGemvThreads) __attribute__((amdgpu_waves_per_eu(4, 4))) void gemv_pk_long_kernel(PkMat m, int N, int K, int C, const void* __restrict__ x_,
+                                                                                                           void* __restrict__ y_) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  uint4* xs = reinterpret_cast<uint4*>(smem);  // [2][64 C]
+  __shared__ float part[R][kGemvThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wid = __builtin_amdgcn_readfirstlane(tid >> 6);  // (a scalar: row addresses stay in SGPRs)
   const int half = wid & 1, pr = wid >> 1;
   const int nvec = K / 8;
   const int hv = ((nvec + 1) / 2 + 63) / 64 * 64;  // chunks of the low half (whole lane sets)
   const int v0 = half * hv, v1 = half ? nvec : (hv < nvec ? hv : nvec);
-  const uint16_t* x = reinterpret_cast<const uint16_t*>(x_);
-  constexpr int RPW = RW * kGemvThreads / 128;  // rows per workgroup pass
+  const int nc = v1 - v0, nsp = (nc + 63) >> 6, nslots = C / 2;
+  constexpr int RPW = R * kGemvThreads / 128;  // rows per workgroup pass
   const int groups = (N + RPW - 1) / RPW;
   auto row_of = [&](int grp, int r) {
-    const int n = grp * RPW + pr * RW + r;
+    const int n = grp * RPW + pr * R + r;
     return n < N ? n : N - 1;
   };
-  uint2 hraw[RW];
+  auto seg_of = [&](int grp, int r) { return m.data + (int64_t)row_of(grp, r) * m.row_bytes + (int64_t)v0 * 12; };
+  // the weight stream starts BEFORE the staging: the headers of this workgroup's first rows and their first pass
+  PkPass<R, SLOTS> pa, pb;
+  uint2 hraw[R];
 #pragma unroll
-  for (int r = 0; r < RW; ++r) hraw[r] = m.hdr[row_of((int)blockIdx.x, r)];
-  uint4 xr[C];
+  for (int r = 0; r < R; ++r) hraw[r] = m.hdr[row_of((int)blockIdx.x, r)];
 #pragma unroll
-  for (int c = 0; c < C; ++c) {
-    const int v = v0 + lane + 64 * c;
-    xr[c] = v < v1 ? *reinterpret_cast<const uint4*>(x + (int64_t)v * 8) : make_uint4(0u, 0u, 0u, 0u);
+  for (int i = 0; i < SLOTS; ++i)
+#pragma unroll
+    for (int r = 0; r < R; ++r) pk_request_slot<true>(pa.lo[i][r], pa.nb[i][r], seg_of((int)blockIdx.x, r), nc, i, lane);
+  {
+    const uint4* x = reinterpret_cast<const uint4*>(x_);
+    const int img = 64 * C, lo_end = hv < nvec ? hv : nvec;
+    uint4 t[8];  // C <= 16: at most 2048 chunk slots, one round trip
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = tid + kGemvThreads * k;
+      const int v = i < img ? i : hv + (i - img);
+      const bool live = i < img ? v < lo_end : (i < 2 * img && v < nvec);
+      t[k] = live ? x[v] : make_uint4(0u, 0u, 0u, 0u);
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const int i = tid + kGemvThreads * k;
+      if (i < 2 * img) xs[i] = t[k];
+    }
   }
+  __syncthreads();
+  const uint4* xh = xs + half * 64 * C + lane;
+  bool first = true;
   for (int grp = blockIdx.x; grp < groups; grp += gridDim.x) {
-    PkPass<RW, SLOTS> ps;
-    PkHdr h[RW];
+    const unsigned char* seg[R];
+    PkHdr h[R];
+    float acc[R];
 #pragma unroll
-    for (int i = 0; i < SLOTS; ++i)
-#pragma unroll
-      for (int r = 0; r < RW; ++r) {
-        const unsigned char* seg = m.data + (int64_t)row_of(grp, r) * m.row_bytes + (int64_t)v0 * 12;
-        if (i < TF) pk_request_slot<false>(ps.lo[i][r], ps.nb[i][r], seg, v1 - v0, i, lane);
-        else pk_request_slot<true>(ps.lo[i][r], ps.nb[i][r], seg, v1 - v0, i, lane);
-      }
-#pragma unroll
-    for (int r = 0; r < RW; ++r) h[r] = pk_uniform(hraw[r]);
-    pk_request_raw<RW, SLOTS>(ps, m, h, v0 >> 6, (v1 - v0 + 63) >> 6, lane);
+    for (int r = 0; r < R; ++r) {
+      seg[r] = seg_of(grp, r);
+      h[r] = pk_uniform(hraw[r]);
+      acc[r] = 0.f;
+    }
     const int nxt = grp + (int)gridDim.x < groups ? grp + (int)gridDim.x : grp;
+    auto request = [&](PkPass<R, SLOTS>& ps, int p0, bool slots) {
+      if (slots) {
 #pragma unroll
-    for (int r = 0; r < RW; ++r) hraw[r] = m.hdr[row_of(nxt, r)];
-    float acc[RW];
+        for (int i = 0; i < SLOTS; ++i)
 #pragma unroll
-    for (int r = 0; r < RW; ++r) acc[r] = 0.f;
-    pk_pass_dot<RW, SLOTS>(m, ps, h, v0 >> 6, SLOTS, lane, acc, [&](int c) -> const uint4& { return xr[c]; });
+          for (int r = 0; r < R; ++r) pk_request_slot<true>(ps.lo[i][r], ps.nb[i][r], seg[r], nc, p0 + i, lane);
+      }
+      const int left = nsp - 2 * p0;  // (a pass of padding only has no span)
+      pk_request_raw<R, SLOTS>(ps, m, h, (v0 >> 6) + 2 * p0, left > 0 ? left : 0, lane);
+    };
+    auto dot = [&](const PkPass<R, SLOTS>& ps, int p0) {
+      pk_pass_dot<R, SLOTS>(m, ps, h, (v0 >> 6) + 2 * p0, nslots - p0, lane, acc, [&](int c) { return xh[64 * (2 * p0 + c)]; });
+    };
+    request(pa, 0, !first);  // (the workgroup's first pass is in flight since before the staging)
+    first = false;
 #pragma unroll
-    for (int r = 0; r < RW; ++r) {
+    for (int r = 0; r < R; ++r) hraw[r] = m.hdr[row_of(nxt, r)];  // the next rows' headers travel with this row's first pass
+    for (int p0 = 0; p0 < nslots; p0 += 2 * SLOTS) {
+      const bool hb = p0 + SLOTS < nslots;
+      if (hb) request(pb, p0 + SLOTS, true);
+      dot(pa, p0);
+      if (hb) {
+        if (p0 + 2 * SLOTS < nslots) request(pa, p0 + 2 * SLOTS, true);
+        dot(pb, p0 + SLOTS);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < R; ++r) {
       acc[r] = wave_sum(acc[r]);
       if (lane == 0 && half) part[r][wid] = acc[r];
     }
     __syncthreads();
 #pragma unroll
-    for (int r = 0; r < RW; ++r) {
-      const int n = grp * RPW + pr * RW + r;
+    for (int r = 0; r < R; ++r) {
+      const int n = grp * RPW + pr * R + r;
       if (lane == 0 && !half && n < N) store1<bf16_t>(y_, n, acc[r] + part[r][wid + 1]);
     }
     __syncthreads();
@@ -181,7 +223,7 @@ extern "C" int dl_gemv_pk(int mode, const void* data, int64_t data_bytes, const 
   } else {
     DL_REQUIRE(x != nullptr, "dl_gemv_pk: missing operand for mode %d", mode);
     DL_REQUIRE((uintptr_t)x % 16 == 0, "dl_gemv_pk: x must be 16-byte aligned");
-    // (the plain launches run at most grid_cap / 2 workgroups, as dl_gemv's: two per CU, which leaves them 256 registers)
+    // (the x-in-registers launches run at most grid_cap / 2 workgroups, as dl_gemv's: two per CU, which leaves them 256 registers)
     const int cap2 = grid_cap / 2 > 0 ? grid_cap / 2 : 1;
     if (K <= 4096) {  // two rows per wave and pass
       const int groups = (N + 7) / 8;
@@ -193,14 +235,13 @@ extern "C" int dl_gemv_pk(int mode, const void* data, int64_t data_bytes, const 
       const dim3 grid((unsigned)(groups < cap2 ? groups : cap2));
       hipLaunchKernelGGL((gemv_pk_plain_kernel<2, 1, 2, 4>), grid, dim3(kGemvThreads), 0, st, m, N, K, x, y);
     } else {
-      // whole passes over a grid that is resident at once: two workgroups per CU (a wave's half of x and the rows in flight take up to 230 registers)
-      const bool c12 = ((K / 8 + 1) / 2 + 63) / 64 <= 12;
-      const int groups = c12 ? (N + 3) / 4 : (N + 1) / 2;  // two rows per wave pair and pass / one
-      const int passes = (groups + cap2 - 1) / cap2;
+      // x in LDS: four workgroups per CU, so the grid is sized from the whole cap; whole passes over a grid that is resident at once.  C: the chunk slots
+      // per lane of a segment that the bf16 kernel dots (12: either half holds at most 12 spans, else 16)
+      const int C = ((K / 8 + 1) / 2 + 63) / 64 <= 12 ? 12 : 16;
+      const int groups = (N + 1) / 2;  // one row per wave pair and pass
+      const int passes = (groups + grid_cap - 1) / grid_cap;
       const dim3 grid((unsigned)((groups + passes - 1) / passes));
-      // 8192 < K <= 12288: either half of a row holds at least three whole pairs; 12288 < K <= 16384: at least five
-      if (c12) hipLaunchKernelGGL((gemv_pk_halves_kernel<12, 2, 2, 3>), grid, dim3(kGemvThreads), 0, st, m, N, K, x, y);
-      else hipLaunchKernelGGL((gemv_pk_halves_kernel<16, 1, 2, 5>), grid, dim3(kGemvThreads), 0, st, m, N, K, x, y);
+      hipLaunchKernelGGL((gemv_pk_long_kernel<1, 3>), grid, dim3(kGemvThreads), (size_t)2 * C * 1024, st, m, N, K, C, x, y);
     }
   }
   DL_CHECK_LAUNCH("dl_gemv_pk");

@@ -201,8 +201,11 @@ class DecodeScheduler:
             return m["qkv"], m["o"], m["gu"], m["down"]
         pk = (getattr(layer, "pk", None) or {}) if self._streams_packed(st) else {}
         pk_qkv = getattr(layer, "pk_qkv", None) if self._streams_packed(st) and self.decode_weight_pack_qkv else None
+        pk_down = pk.get("down")
+        if pk_down is None and self._streams_packed(st) and self.decode_weight_pack_down:  # long rows only (model._pack_decode_weights)
+            pk_down = getattr(layer, "pk_down", None)
         src = lambda p, w: w if p is None else p
-        return src(pk_qkv, layer.w_qkv), src(pk.get("o"), layer.self_attn.o_proj.weight), src(pk.get("gu"), layer.w_gu), src(pk.get("down"), layer.mlp.down_proj.weight)
+        return src(pk_qkv, layer.w_qkv), src(pk.get("o"), layer.self_attn.o_proj.weight), src(pk.get("gu"), layer.w_gu), src(pk_down, layer.mlp.down_proj.weight)
 
     def _lm_head_stream(self, st):
         """The vocabulary projection's source, chosen as _layer_streams chooses (it has no MXFP8 codes)."""
@@ -464,7 +467,7 @@ class DecodeScheduler:
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
-               self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
+               self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.decode_weight_pack_down, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
                self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)),
                bool(getattr(self, "_processed", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured, and whether dl_logits_process runs in front of it; the sampling parameters, the labels and the processors' settings are device data, not part of the key)
         if not self.use_hip_graph:

@@ -78,11 +78,16 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         # the same bits out, ~0.79 of the bytes in.  The packed copies are made by finalize(); DL_WEIGHT_PACK=0: not made, not used
         self.decode_weight_pack = os.environ.get("DL_WEIGHT_PACK", "1") == "1"
         # ... o_proj and down_proj too.  Off: their packed launches (x in registers, one short stream per launch) measured no faster than the bf16 ones
-        # (o 6.8 vs 6.7 us, down 17.0 vs 16.3 us), so only gate|up and the vocabulary projection are packed by default
+        # (o 6.8 vs 6.7 us, down 17.0 vs 16.3 us), so only gate|up and the vocabulary projection are packed by default (down_proj's long
+        # rows have since got a faster packed kernel and a knob of their own, decode_weight_pack_down below)
         self.decode_weight_pack_plain = os.environ.get("DL_WEIGHT_PACK_PLAIN", "0") == "1"
         # ... and every layer's q|k|v, which streams inside the fused q|k|v + attention launch (dl_gemv_qkv_attn_pk; the unfused launch: dl_gemv_pk).  The copy is
         # kept as layer.pk_qkv, beside layer.pk.  DL_WEIGHT_PACK_QKV=0: not made, not used (+2.5 GB of copies at 7B when on)
         self.decode_weight_pack_qkv = os.environ.get("DL_WEIGHT_PACK_QKV", "1") == "1"
+        # ... and every layer's down_proj with long rows (K > 8192: 7B 11008, 13B 13824), whose packed launch keeps x in LDS at four workgroups per CU and beats
+        # the bf16 one by 1.2-1.7 us at K = 11008 (stage 3).  The copy is kept as layer.pk_down, beside layer.pk (with decode_weight_pack_plain it IS
+        # layer.pk["down"]).  DL_WEIGHT_PACK_DOWN=0: not made, not used (+2.3 GB of copies at 7B when on)
+        self.decode_weight_pack_down = os.environ.get("DL_WEIGHT_PACK_DOWN", "1") == "1"
         # attention workgroups per head inside the fused launch: up to this many, one per 128 keys of the scheduled bound (DL_QA_SPLITS=1: always one)
         self.fused_attn_max_splits = max(1, min(4, int(os.environ.get("DL_QA_SPLITS", "4"))))  # the kernel takes 1..4 (kQaMaxSplits)
         self.gu_grid_cap = int(os.environ.get("DL_GU_GRID", "0"))  # workgroups of the batch-1 gate|up launch (0: the kernel's default, 1024)
@@ -271,12 +276,14 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         projection; with decode_weight_pack_plain also o_proj and down_proj.  Rebuilt by every finalize() -- i.e. whenever the weight fingerprint (lm_head included) moves -- and dropped
         for MXFP8 decoder weights, whose step streams the codes.  A matrix the kernel does not take (gemv_pk_ok) or that would not shrink below 0.9 of its
         size (pack() returns None) keeps its model-dtype launch.  With decode_weight_pack_qkv every layer's q|k|v is packed too, under the same rules, as
-        layer.pk_qkv (not part of layer.pk: the fused q|k|v + attention launch streams it through dl_gemv_qkv_attn_pk)."""
+        layer.pk_qkv (not part of layer.pk: the fused q|k|v + attention launch streams it through dl_gemv_qkv_attn_pk), and with decode_weight_pack_down every
+        layer's down_proj with K > 8192 as layer.pk_down (the same object as layer.pk["down"] where decode_weight_pack_plain has made that one)."""
         from . import bf16pack
 
         for l in self.model.layers:
             l.pk = None
             l.pk_qkv = None
+            l.pk_down = None
         self._pk_lm_head = None
         if not self.decode_weight_pack or self.decode_weight_format is not None or self.dtype != torch.bfloat16:
             return
@@ -288,6 +295,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                     "down": pk(l.mlp.down_proj.weight.data, ops.GEMV_PLAIN) if plain else None}
             if self.decode_weight_pack_qkv:
                 l.pk_qkv = pk(l.w_qkv, A)
+            if self.decode_weight_pack_down and l.mlp.down_proj.weight.shape[1] > 8192:
+                l.pk_down = l.pk["down"] if plain else pk(l.mlp.down_proj.weight.data, ops.GEMV_PLAIN)
         self._pk_lm_head = pk(self.lm_head.weight.data, A)
 
     def weight_pack_bytes(self) -> dict:
@@ -298,8 +307,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if getattr(self, "_pk_lm_head", None) is not None:
             ps.append(self._pk_lm_head)
         qs = [l.pk_qkv for l in self.model.layers if getattr(l, "pk_qkv", None) is not None]
-        return {"matrices": len(ps), "packed": sum(bf16pack.packed_nbytes(p) for p in ps), "bf16": sum(bf16pack.raw_nbytes(p) for p in ps),
-                "qkv": {"matrices": len(qs), "packed": sum(bf16pack.packed_nbytes(p) for p in qs), "bf16": sum(bf16pack.raw_nbytes(p) for p in qs)}}
+        # (a pk_down that is layer.pk["down"] is counted there, once)
+        ds = [l.pk_down for l in self.model.layers if getattr(l, "pk_down", None) is not None and l.pk_down is not (l.pk or {}).get("down")]
+        side = lambda xs: {"matrices": len(xs), "packed": sum(bf16pack.packed_nbytes(p) for p in xs), "bf16": sum(bf16pack.raw_nbytes(p) for p in xs)}
+        return {"matrices": len(ps), "packed": sum(bf16pack.packed_nbytes(p) for p in ps), "bf16": sum(bf16pack.raw_nbytes(p) for p in ps), "qkv": side(qs), "down": side(ds)}
 
     def _quantize_decoder_weights(self):
         from .mxfp8 import dequantize_mx8
@@ -405,7 +416,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         return {
             "use_hip_graph": self.use_hip_graph, "attn_inkernel_combine": self.attn_inkernel_combine, "device_prompt_layout": self.device_prompt_layout,
             "tp_side_stream": self.tp_side_stream, "gemv_max_decode_batch": self.gemv_max_decode_batch, "smallm_max_decode_batch": self.smallm_max_decode_batch,
-            "fuse_qkv_attn": self.fuse_qkv_attn, "fuse_gu_tp": self.fuse_gu_tp, "decode_weight_pack": self.decode_weight_pack, "decode_weight_pack_plain": self.decode_weight_pack_plain, "decode_weight_pack_qkv": self.decode_weight_pack_qkv, "fused_attn_max_splits": self.fused_attn_max_splits, "gu_grid_cap": self.gu_grid_cap,
+            "fuse_qkv_attn": self.fuse_qkv_attn, "fuse_gu_tp": self.fuse_gu_tp, "decode_weight_pack": self.decode_weight_pack, "decode_weight_pack_plain": self.decode_weight_pack_plain, "decode_weight_pack_qkv": self.decode_weight_pack_qkv, "decode_weight_pack_down": self.decode_weight_pack_down, "fused_attn_max_splits": self.fused_attn_max_splits, "gu_grid_cap": self.gu_grid_cap,
             "qkv_attn_grid_cap": self.qkv_attn_grid_cap, "splitk_o_proj": self.splitk_o_proj, "packed_prefill_gemm": self.packed_prefill_gemm, "packed_down_proj": self.packed_down_proj, "packed_qkv_parts": self.packed_qkv_parts, "packed_decode_mlp": self.packed_decode_mlp, "packed_decode_mlp_min_batch": self.packed_decode_mlp_min_batch, "packed_decode_qkv_min_batch": self.packed_decode_qkv_min_batch, "packed_decode_qkv_parts": self.packed_decode_qkv_parts, "packed_decode_qkv_parts_max_batch": self.packed_decode_qkv_parts_max_batch,
             "smallm_wide_slices": self.smallm_wide_slices, "decode_sync_every": self.decode_sync_every, "prefill_width_bucket": self.prefill_width_bucket,
             "max_prefill_graphs": self.max_prefill_graphs,

@@ -5,7 +5,7 @@ import torch
 from dynamic_llava_amd import hip_ops as ops, bf16pack as bp
 
 A, PAIR = ops.GEMV_ADDNORM, ops.GEMV_OUT_SILU_PAIR
-SHAPES = [("o", 4096, 4096, 0), ("gate|up", 22016, 4096, A | PAIR), ("down", 4096, 11008, 0), ("lm_head", 32000, 4096, A)]
+SHAPES = [("o", 4096, 4096, 0), ("gate|up", 22016, 4096, A | PAIR), ("down", 4096, 11008, 0), ("down 13B", 5120, 13824, 0), ("lm_head", 32000, 4096, A)]
 NCOPY = 6
 REPS = 10
 for name, N, K, mode in SHAPES:
