@@ -1,6 +1,6 @@
 // Device-side logits processors: repetition penalty, no-repeat n-gram and bad-word bans of one decode step, the stage HF's generate() runs in front of
 // the selection rule (RepetitionPenaltyLogitsProcessor, NoRepeatNGramLogitsProcessor, NoBadWordsLogitsProcessor, in that order).  It sits between the
-// lm_head launch and the bookkeeping launch (dl_decode_advance / dl_decode_sample), which consume its fp32 output unchanged.
+// lm_head launch and the bookkeeping launch (dl_decode_advance in advance.hip / dl_decode_sample in sample.hip), which consume its fp32 output unchanged.
 // The rule is dynamic_llava_amd/logits_rules.py (the contract this kernel is tested against); in short, per row, with g = the row's tokens emitted so
 // far (out_ids[b, 0 : min(step[b], out_cap)]) and s = len(g):
 //   y_v = float32(logit_v);

@@ -1,6 +1,6 @@
 // F1: VisionPredictor (DML:1308-1359 + CTL:126-180,276-323) -> keep/drop logits + log-softmax score.
 // F6: TextPredictor (DML:1362-1387) + decision (DML:2388-2391).
-// Decode-step bookkeeping: greedy argmax + device-side KV length advance (replaces CU:153-164's host sync).
+// (The greedy decode-step closing that consumes the text predictor's decision is advance.hip.)
 //
 // The vision predictor is a fixed pipeline of launches on the caller's stream, built from dl_layernorm,
 // dl_linear (MFMA, fused bias/GELU/residual epilogues) and dl_attn_prefill (non-causal) plus three small
@@ -97,106 +97,6 @@ __global__ __launch_bounds__(512) void tp_stage2b_kernel(const float* __restrict
                                                           const void* b7, float* __restrict__ logits, int32_t* __restrict__ decision, int D) {
   extern __shared__ float tp_sm[];  // [D/2] + [D/4] + [2]
   tp_stage2b_body<T>(a1g, w5, b5, w7, b7, logits, decision, D, (int)blockIdx.x, tp_sm);
-}
-
-// ---- greedy argmax + device-side bookkeeping.  grid (B).  The row (V logits) is read with 16-byte loads, 4 per thread in flight
-// (one round trip for V <= 32768), and thread 0 requests the per-row state it will update before the reduction ----
-template <typename T>
-__global__ __launch_bounds__(1024) void decode_advance_kernel(const void* __restrict__ logits, int64_t row_stride, int V,
-                                                               int64_t* __restrict__ next_ids, int64_t* __restrict__ out_ids, int out_cap,
-                                                               int32_t* __restrict__ step, int32_t* __restrict__ finished, int eos_id,
-                                                               int eos_id2, int eos_id3, int pad_id, int32_t* __restrict__ kv_len_full,
-                                                               int32_t* __restrict__ kv_len_sparse, const int32_t* __restrict__ decision,
-                                                               int min_new_tokens) {
-  constexpr int VE = Elem<T>::kVec;
-  using S = typename Elem<T>::storage;
-  __shared__ float smax[16];
-  __shared__ int sidx[16];
-  const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int st_fin = 0, st_step = 0, st_dec = 1, st_full = 0, st_sparse = 0;
-  if (tid == 0) {
-    if (finished) st_fin = finished[b];
-    if (step) st_step = step[b];
-    if (decision) st_dec = decision[b];
-    if (kv_len_full) st_full = kv_len_full[b];
-    if (kv_len_sparse) st_sparse = kv_len_sparse[b];
-  }
-  const S* row = reinterpret_cast<const S*>(logits) + (int64_t)b * row_stride;
-  const bool vec_ok = (row_stride % VE == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
-  // HF MinNewTokensLengthLogitsProcessor: the EOS logit is -inf while fewer than min_new_tokens tokens exist (uniform per row)
-  // (all EOS ids of the set: eos_id2 / eos_id3 are -1 when unused, and no vocabulary index is negative)
-  const bool ban = eos_id >= 0 && min_new_tokens > 0 && (step ? step[b] : 0) < min_new_tokens;
-  const int banned = ban ? eos_id : -1, banned2 = ban ? eos_id2 : -1, banned3 = ban ? eos_id3 : -1;
-  float best = -INFINITY;
-  int bi = 0x7fffffff;
-  const int n_chunks = V / VE;
-  if (vec_ok) {
-    for (int c0 = 0; c0 < n_chunks; c0 += 4 * 1024) {
-      float x[4][VE];
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int c = c0 + u * 1024 + tid;
-        if (c < n_chunks) load16<T>(row + (int64_t)c * VE, x[u]);
-      }
-#pragma unroll
-      for (int u = 0; u < 4; ++u) {
-        const int c = c0 + u * 1024 + tid;
-        if (c < n_chunks)
-#pragma unroll
-          for (int e = 0; e < VE; ++e) {
-            const int v = c * VE + e;
-            if (v == banned || v == banned2 || v == banned3) continue;
-            if (x[u][e] > best || (x[u][e] == best && v < bi)) {
-              best = x[u][e];
-              bi = v;
-            }
-          }
-      }
-    }
-  }
-  for (int v = (vec_ok ? n_chunks * VE : 0) + tid; v < V; v += 1024) {  // tail (or the whole row when it is not 16-byte addressable)
-    const float xv = load1<T>(logits, (int64_t)b * row_stride + v);
-    if (v == banned || v == banned2 || v == banned3) continue;
-    if (xv > best || (xv == best && v < bi)) {
-      best = xv;
-      bi = v;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) {
-      best = ob;
-      bi = oi;
-    }
-  }
-  if (lane == 0) {
-    smax[wid] = best;
-    sidx[wid] = bi;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    const int nw = blockDim.x >> 6;
-    for (int w = 1; w < nw; ++w)
-      if (smax[w] > best || (smax[w] == best && sidx[w] < bi)) {
-        best = smax[w];
-        bi = sidx[w];
-      }
-    if (bi == 0x7fffffff) bi = 0;
-    int tok = bi;
-    if (finished) {
-      if (st_fin) tok = pad_id;
-      else if (eos_id >= 0 && (tok == eos_id || tok == eos_id2 || tok == eos_id3)) finished[b] = 1;
-    }
-    next_ids[b] = tok;
-    if (out_ids && step) {
-      if (st_step < out_cap) out_ids[(int64_t)b * out_cap + st_step] = tok;
-      step[b] = st_step + 1;
-    }
-    if (kv_len_full) kv_len_full[b] = st_full + 1;
-    if (kv_len_sparse) kv_len_sparse[b] = st_sparse + st_dec;
-  }
 }
 
 }  // namespace dl
@@ -309,20 +209,5 @@ extern "C" int dl_text_predictor_decide(const void* x, int64_t x_row_stride, int
                        w->l5_b, w->l7_w, w->l7_b, logits_out, decision, D);
   });
   DL_CHECK_LAUNCH("dl_text_predictor_decide");
-  return DL_OK;
-}
-
-extern "C" int dl_decode_advance(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B, int64_t* next_ids,
-                                 int64_t* out_ids, int out_cap, int32_t* step, int32_t* finished, int eos_id, int eos_id2, int eos_id3, int pad_id,
-                                 int32_t* kv_len_full, int32_t* kv_len_sparse, const int32_t* decision, int min_new_tokens,
-                                 void* stream) {
-  DL_REQUIRE(logits && next_ids, "dl_decode_advance: NULL pointer");
-  DL_REQUIRE(B > 0 && V > 0, "dl_decode_advance: bad shape");
-  hipStream_t st = as_stream(stream);
-  DL_DISPATCH_DTYPE(logits_dtype, T, {
-    hipLaunchKernelGGL((decode_advance_kernel<T>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, next_ids, out_ids,
-                       out_cap, step, finished, eos_id, eos_id >= 0 ? eos_id2 : -1, eos_id >= 0 ? eos_id3 : -1, pad_id, kv_len_full, kv_len_sparse, decision, min_new_tokens);
-  });
-  DL_CHECK_LAUNCH("dl_decode_advance");
   return DL_OK;
 }

@@ -1,4 +1,4 @@
-// Device-side sampling: temperature, top-k, top-p and the draw of one decode step, with dl_decode_advance's bookkeeping.
+// Device-side sampling: temperature, top-k, top-p and the draw of one decode step, closed like dl_decode_advance's (advance.hip) by step_close.h.
 // The rule is dynamic_llava_amd/sampling.py (the contract this kernel is tested against); in short, per row:
 //   z = logit / T (IEEE division); banned ids (EOS while step < min_new_tokens) are out;
 //   top-k keeps z >= (k-th largest z), ties included; w = expf(z - zmax), m = floor(w * 2^40) as a 64-bit integer;
@@ -18,6 +18,7 @@
 // the per-thread kept masses (index order = thread order) and a walk over one thread's registers.  Every loop has a fixed trip count; no workspace.
 #include "dl_common.h"
 #include "fixed_mass.h"
+#include "step_close.h"
 
 namespace dl {
 
@@ -69,7 +70,7 @@ struct dl_sample_params_dev {  // == dl_sample_params (include/dynllava.h)
 template <typename T, int R>
 __global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restrict__ logits, int64_t row_stride, int V, int64_t* __restrict__ next_ids,
                                                               int64_t* __restrict__ out_ids, int out_cap, int32_t* __restrict__ step,
-                                                              int32_t* __restrict__ finished, int eos_id, int eos_id2, int eos_id3, int pad_id,
+                                                              int32_t* __restrict__ finished, EosSet eos, int pad_id,
                                                               int32_t* __restrict__ kv_len_full, int32_t* __restrict__ kv_len_sparse,
                                                               const int32_t* __restrict__ decision, int min_new_tokens,
                                                               const dl_sample_params_dev* __restrict__ prm, uint8_t* __restrict__ kept_mask) {
@@ -89,20 +90,16 @@ __global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restr
   __shared__ unsigned long long s_thr;
   __shared__ int s_bin, s_tok;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int st_fin = 0, st_step = 0, st_dec = 1, st_full = 0, st_sparse = 0;
+  const StepClose sc = {next_ids, out_ids, out_cap, step, finished, pad_id, kv_len_full, kv_len_sparse, decision};
+  StepRow st;
   if (tid == 0) {
-    if (finished) st_fin = finished[b];
-    if (step) st_step = step[b];
-    if (decision) st_dec = decision[b];
-    if (kv_len_full) st_full = kv_len_full[b];
-    if (kv_len_sparse) st_sparse = kv_len_sparse[b];
+    st.preload(sc, b);
     s_tok = 0;
   }
-  const int cur_step = step ? step[b] : 0;        // uniform over the workgroup
-  const int row_done = finished ? finished[b] : 0;  // a finished row emits pad_id whatever its logits say: nothing to select
+  const int cur_step = sc.step ? sc.step[b] : 0;        // uniform over the workgroup
+  const int row_done = sc.finished ? sc.finished[b] : 0;  // a finished row emits pad_id whatever its logits say: nothing to select
   if (!row_done) {
-    const bool ban = eos_id >= 0 && min_new_tokens > 0 && cur_step < min_new_tokens;
-    const int banned = ban ? eos_id : -1, banned2 = ban ? eos_id2 : -1, banned3 = ban ? eos_id3 : -1;
+    const EosSet banned = banned_ids(eos, min_new_tokens, cur_step);  // (compared id by id below: through EosSet::has the R = 8 rows allocate other registers)
     const float temp = prm->temperature;  // finite and > 0: validated by the host (sampling.normalize_params) before the block is written
     const int top_k = prm->top_k;
     const float top_p = prm->top_p;
@@ -121,24 +118,12 @@ __global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restr
 #pragma unroll
     for (int r = 0; r < R; ++r) {
       const int v0 = (int)fresh((uint32_t)((tid * R + r) * VE));
-      uint4 q = make_uint4(0u, 0u, 0u, 0u);
-      if (vec_ok && v0 + VE <= V) {
-        q = *reinterpret_cast<const uint4*>(row + v0);
-      } else {
-        uint32_t t4[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-        for (int e = 0; e < VE; ++e) {
-          if (v0 + e < V) {
-            t4[e >> 1] |= (uint32_t)row[v0 + e] << (16 * (e & 1));
-          }
-        }
-        q = make_uint4(t4[0], t4[1], t4[2], t4[3]);
-      }
+      const uint4 q = row_chunk<T>(row, v0, V, vec_ok);
       const uint32_t q4[4] = {q.x, q.y, q.z, q.w};
 #pragma unroll
       for (int e = 0; e < VE; ++e) {
         const int v = v0 + e;
-        if (v < V && v != banned && v != banned2 && v != banned3) valid[(r * VE + e) >> 5] |= 1u << ((r * VE + e) & 31);
+        if (v < V && v != banned.id && v != banned.id2 && v != banned.id3) valid[(r * VE + e) >> 5] |= 1u << ((r * VE + e) & 31);
       }
 #pragma unroll
       for (int i = 0; i < 4; ++i) raw[r * 4 + i] = q4[i];
@@ -148,7 +133,7 @@ __global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restr
     auto is_valid = [&](int j) -> bool {
       if constexpr (kStream) {
         const int v = tid * ne + j;
-        return v < V && v != banned && v != banned2 && v != banned3;
+        return v < V && v != banned.id && v != banned.id2 && v != banned.id3;
       } else {
         return (fresh(valid[j >> 5]) >> (j & 31)) & 1u;
       }
@@ -315,20 +300,7 @@ __global__ __launch_bounds__(1024) void decode_sample_kernel(const void* __restr
     }
   }
   __syncthreads();
-  if (tid == 0) {  // dl_decode_advance's bookkeeping, statement for statement
-    int tok = s_tok;
-    if (finished) {
-      if (st_fin) tok = pad_id;
-      else if (eos_id >= 0 && (tok == eos_id || tok == eos_id2 || tok == eos_id3)) finished[b] = 1;
-    }
-    next_ids[b] = tok;
-    if (out_ids && step) {
-      if (st_step < out_cap) out_ids[(int64_t)b * out_cap + st_step] = tok;
-      step[b] = st_step + 1;
-    }
-    if (kv_len_full) kv_len_full[b] = st_full + 1;
-    if (kv_len_sparse) kv_len_sparse[b] = st_sparse + st_dec;
-  }
+  if (tid == 0) st.commit(s_tok, sc, eos, b);
 }
 
 }  // namespace dl
@@ -347,19 +319,12 @@ extern "C" int dl_decode_sample(const void* logits, int logits_dtype, int64_t lo
   DL_REQUIRE(V <= kSampleMaxV, "dl_decode_sample: V=%d exceeds %d (64-bit fixed-point masses)", V, kSampleMaxV);
   hipStream_t st = as_stream(stream);
   const dl_sample_params_dev* prm = reinterpret_cast<const dl_sample_params_dev*>(params);
-  const int e2 = eos_id >= 0 ? eos_id2 : -1, e3 = eos_id >= 0 ? eos_id3 : -1;
-#define DL_SAMPLE_LAUNCH(T, R)                                                                                                                  \
-  hipLaunchKernelGGL((decode_sample_kernel<T, R>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, next_ids, out_ids, out_cap, \
-                     step, finished, eos_id, e2, e3, pad_id, kv_len_full, kv_len_sparse, decision, min_new_tokens, prm, kept_mask)
   DL_DISPATCH_DTYPE(logits_dtype, T, {
-    if constexpr (Elem<T>::kVec == 8) {
-      if (V <= 1024 * 4 * 8) DL_SAMPLE_LAUNCH(T, 4);
-      else DL_SAMPLE_LAUNCH(T, 8);
-    } else {
-      DL_SAMPLE_LAUNCH(T, 0);
-    }
+    DL_DISPATCH_ROW_REGS(T, V, R, {
+      hipLaunchKernelGGL((decode_sample_kernel<T, R>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, next_ids, out_ids,
+                         out_cap, step, finished, eos_set(eos_id, eos_id2, eos_id3), pad_id, kv_len_full, kv_len_sparse, decision, min_new_tokens, prm, kept_mask);
+    });
   });
-#undef DL_SAMPLE_LAUNCH
   DL_CHECK_LAUNCH("dl_decode_sample");
   return DL_OK;
 }

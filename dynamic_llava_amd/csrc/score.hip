@@ -1,5 +1,5 @@
-// Device-side teacher-forced scoring: the negative log-likelihood of one labelled token per row, with dl_decode_advance's bookkeeping around
-// the LABEL as the next token (the reference's perplexity driver, model_lvis_for_ppl.py:136-191: score the label, feed the label).
+// Device-side teacher-forced scoring: the negative log-likelihood of one labelled token per row; the step is closed like dl_decode_advance's
+// (advance.hip) by step_close.h, around the LABEL as the next token (the reference's perplexity driver, model_lvis_for_ppl.py:136-191: score the label, feed the label).
 // The rule is dynamic_llava_amd/scoring.py (the contract this kernel is tested against); in short, per row:
 //   m = max_v x_v (fp32), top1 = lowest index attaining it; mass_v = floor(expf(x_v - m) * 2^40) as a 64-bit integer; M = sum_v mass_v;
 //   lse = logf(float(M) * 2^-40); nll = (m - x_label) + lse.
@@ -12,6 +12,7 @@
 // reduction.  Every loop has a fixed trip count; no workspace, no global atomics, nothing that synchronises with the host.
 #include "dl_common.h"
 #include "fixed_mass.h"
+#include "step_close.h"
 
 namespace dl {
 
@@ -31,16 +32,12 @@ __global__ __launch_bounds__(1024) void decode_score_kernel(const void* __restri
   __shared__ unsigned long long s_sum[16];
   __shared__ float s_xlab;
   const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-  int st_step = 0, st_dec = 1, st_full = 0, st_sparse = 0;
-  if (tid == 0) {
-    if (step) st_step = step[b];
-    if (decision) st_dec = decision[b];
-    if (kv_len_full) st_full = kv_len_full[b];
-    if (kv_len_sparse) st_sparse = kv_len_sparse[b];
-  }
+  const StepClose sc = {next_ids, out_ids, out_cap, step, finished, pad_id, kv_len_full, kv_len_sparse, decision};
+  StepRow st;
+  if (tid == 0) st.preload(sc, b, false);  // (a finished row has no label: its pick is pad_id already)
   // uniform over the workgroup: the slot and its label.  A label outside [0, V) is never used as an index: it means "no label".
-  const int cur_step = step ? step[b] : 0;
-  const int row_done = finished ? finished[b] : 0;
+  const int cur_step = sc.step ? sc.step[b] : 0;
+  const int row_done = sc.finished ? sc.finished[b] : 0;
   int lab = -1;
   if (!row_done && cur_step >= 0 && cur_step < label_cap) {
     const int64_t l = labels[(int64_t)b * label_cap + cur_step];
@@ -53,20 +50,7 @@ __global__ __launch_bounds__(1024) void decode_score_kernel(const void* __restri
     const S* row = reinterpret_cast<const S*>(logits) + (int64_t)b * row_stride;
     const bool vec_ok = (row_stride % VE == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0);
     const int n_chunks = (V + VE - 1) / VE;  // (the last one may be partial)
-    // chunk c's 16 bytes; entries at or past V are zero bits that nobody looks at
-    auto fetch = [&](int c) -> uint4 {
-      const int v0 = c * VE;
-      if (vec_ok && v0 + VE <= V) return *reinterpret_cast<const uint4*>(row + v0);
-      uint32_t t4[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-      for (int e = 0; e < VE; ++e) {
-        if (v0 + e < V) {
-          if constexpr (VE == 4) t4[e] = __float_as_uint((float)row[v0 + e]);
-          else t4[e >> 1] |= (uint32_t)row[v0 + e] << (16 * (e & 1));
-        }
-      }
-      return make_uint4(t4[0], t4[1], t4[2], t4[3]);
-    };
+    auto fetch = [&](int c) -> uint4 { return row_chunk<T>(row, c * VE, V, vec_ok); };
     auto elem = [](const uint4& q, int e) -> float {
       const uint32_t q4[4] = {q.x, q.y, q.z, q.w};
       if constexpr (VE == 4) return __uint_as_float(q4[e]);
@@ -103,33 +87,8 @@ __global__ __launch_bounds__(1024) void decode_score_kernel(const void* __restri
 #pragma unroll
       for (int r = 0; r < R; ++r) visit1(r * 1024 + tid, raw[r]);
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ob = __shfl_xor(best, o, 64);
-      const int oi = __shfl_xor(bi, o, 64);
-      if (ob > best || (ob == best && oi < bi)) {
-        best = ob;
-        bi = oi;
-      }
-    }
-    if (lane == 0) {
-      s_max[wid] = best;
-      s_idx[wid] = bi;
-    }
-    if (mine) s_xlab = xl;  // exactly one thread
-    __syncthreads();
-    best = s_max[0];
-    bi = s_idx[0];
-#pragma unroll
-    for (int w = 1; w < 16; ++w) {
-      const float ob = s_max[w];
-      const int oi = s_idx[w];
-      if (ob > best || (ob == best && oi < bi)) {
-        best = ob;
-        bi = oi;
-      }
-    }
-    if (bi == 0x7fffffff) bi = 0;
+    if (mine) s_xlab = xl;  // exactly one thread (read after block_argmax's barrier)
+    block_argmax(best, bi, s_max, s_idx, lane, wid);
     m = best;
 
     // ---- pass 2: M = sum of floor(expf(x - m) * 2^40), a 64-bit integer sum ----
@@ -154,8 +113,8 @@ __global__ __launch_bounds__(1024) void decode_score_kernel(const void* __restri
     if (lane == 0) s_sum[wid] = (unsigned long long)acc;
   }
   __syncthreads();
-  if (tid == 0) {  // dl_decode_advance's bookkeeping, statement for statement, around the label (no EOS set: the label sequence ends the row)
-    int tok = pad_id;
+  if (tid == 0) {  // the closing around the label (no EOS set: the label sequence ends the row)
+    int tok = sc.pad_id;
     if (have) {
       uint64_t M = 0;
 #pragma unroll
@@ -165,16 +124,10 @@ __global__ __launch_bounds__(1024) void decode_score_kernel(const void* __restri
       nll[(int64_t)b * label_cap + cur_step] = d + lse;
       if (top1) top1[(int64_t)b * label_cap + cur_step] = bi;
       tok = lab;
-    } else if (finished) {
-      finished[b] = 1;  // labels exhausted
+    } else if (sc.finished) {
+      sc.finished[b] = 1;  // labels exhausted: the scorer's own rule, in front of the shared one
     }
-    next_ids[b] = tok;
-    if (out_ids && step) {
-      if (st_step < out_cap) out_ids[(int64_t)b * out_cap + st_step] = tok;
-      step[b] = st_step + 1;
-    }
-    if (kv_len_full) kv_len_full[b] = st_full + 1;
-    if (kv_len_sparse) kv_len_sparse[b] = st_sparse + st_dec;
+    st.commit(tok, sc, kNoEos, b);
   }
 }
 
@@ -190,18 +143,12 @@ extern "C" int dl_decode_score(const void* logits, int logits_dtype, int64_t log
   DL_REQUIRE(B > 0 && V > 0 && label_cap > 0 && out_cap >= 0, "dl_decode_score: bad shape");
   DL_REQUIRE(V <= kSampleMaxV, "dl_decode_score: V=%d exceeds %d (64-bit fixed-point masses)", V, kSampleMaxV);
   hipStream_t st = as_stream(stream);
-#define DL_SCORE_LAUNCH(T, R)                                                                                                                         \
-  hipLaunchKernelGGL((decode_score_kernel<T, R>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, labels, label_cap, nll, top1, \
-                     next_ids, out_ids, out_cap, step, finished, pad_id, kv_len_full, kv_len_sparse, decision)
   DL_DISPATCH_DTYPE(logits_dtype, T, {
-    if constexpr (Elem<T>::kVec == 8) {
-      if (V <= 1024 * 4 * 8) DL_SCORE_LAUNCH(T, 4);
-      else DL_SCORE_LAUNCH(T, 8);
-    } else {
-      DL_SCORE_LAUNCH(T, 0);
-    }
+    DL_DISPATCH_ROW_REGS(T, V, R, {
+      hipLaunchKernelGGL((decode_score_kernel<T, R>), dim3((unsigned)B), dim3(1024), 0, st, logits, logits_row_stride, V, labels, label_cap, nll, top1,
+                         next_ids, out_ids, out_cap, step, finished, pad_id, kv_len_full, kv_len_sparse, decision);
+    });
   });
-#undef DL_SCORE_LAUNCH
   DL_CHECK_LAUNCH("dl_decode_score");
   return DL_OK;
 }

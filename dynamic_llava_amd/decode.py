@@ -20,6 +20,18 @@ from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
 
 
+@dataclass(frozen=True)
+class StepMode:
+    """How the current request closes its steps (_bookkeep): which kernel picks the token and the host-side constants of the rule it then applies.  Hashable:
+    one element of the graph keys."""
+    eos: object = -1  # -1 (none), one id, or a tuple of up to three (the EOS set)
+    pad: int = 0
+    min_new: int = 0  # EOS is banned while step < min_new (HF semantics)
+    sampled: bool = False  # dl_decode_sample: generate(do_sample=True, seed=...)
+    forced: bool = False  # dl_decode_score: score() -- score the label, feed the label
+    processed: bool = False  # dl_logits_process in front of the kernel; an all-neutral request is exactly the request without the keywords
+
+
 class _DecodeState:
     def __init__(self, model, B, device, dtype, out_cap):
         cfg = model.config
@@ -148,24 +160,24 @@ class DecodeScheduler:
         else:
             self._decode_step_gemm(st, cache)
         if advance:
-            self._bookkeep(st, cache, getattr(self, "_min_new", 0))
+            self._bookkeep(st, cache)
 
-    def _bookkeep(self, st, cache, min_new):
+    def _bookkeep(self, st, cache):
         """The launch that closes a step: pick the token (argmax, a sampled one, or the label, scored), append it, set the EOS flags and advance the KV lengths
         by the predictor's decision.  cache None: the first token -- the prompt's KV lengths are already in place, so neither they nor the decision are passed."""
         lf, ls = (None, None) if cache is None else (cache.len_full, cache.len_sparse)
         dec = st.decision if cache is not None and self._use_tp() else None
-        logits = st.logits
-        if getattr(self, "_processed", False):  # generate() with logits processors: they edit the step's logits on the row's own history (HF's order: before the selection rule)
-            if getattr(self, "_forced", False):
+        logits, m = st.logits, self._mode
+        if m.processed:  # generate() with logits processors: they edit the step's logits on the row's own history (HF's order: before the selection rule)
+            if m.forced:
                 raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
             logits = ops.logits_process(st.logits, st.proc_logits, st.logits_params, st.out_ids, st.step, st.bad_words)
-        if getattr(self, "_forced", False):  # score(): the same bookkeeping around the label, scored
-            ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, self._pad, lf, ls, dec)
-        elif getattr(self, "_sampled", False):  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
-            ops.decode_sample(logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+        if m.forced:  # score(): the same bookkeeping around the label, scored
+            ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, m.pad, lf, ls, dec)
+        elif m.sampled:  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
+            ops.decode_sample(logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
         else:  # EOS is banned while step < min_new (HF semantics)
-            ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, self._eos, self._pad, lf, ls, dec, min_new_tokens=min_new)
+            ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
 
     def _use_tp(self):
         """The output text predictor decides in the decode step (it sits in front of a layer that exists)."""
@@ -465,11 +477,10 @@ class DecodeScheduler:
         nH, SL = cfg.num_attention_heads, cfg.sparse_config["sparse_layer"]
         splits = (cache.n_splits(0, st.B * nH), cache.n_splits(min(SL, cfg.num_hidden_layers - 1), st.B * nH), cache.n_splits(cfg.num_hidden_layers - 1, st.B * nH))
         fused_ns = (cache.fused_attn_splits(0, self.fused_attn_max_splits), cache.fused_attn_splits(cfg.num_hidden_layers - 1, self.fused_attn_max_splits)) if (st.B == 1 and st.qa_gran is not None) else (1, 1)
-        key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(), self._eos, self._pad, getattr(self, "_min_new", 0),
+        key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
                self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.decode_weight_pack_down, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
-               self._kv_format_key(cache), bool(getattr(self, "_sampled", False)), bool(getattr(self, "_forced", False)),
-               bool(getattr(self, "_processed", False)))  # (sampled, scored or greedy: which bookkeeping kernel was captured, and whether dl_logits_process runs in front of it; the sampling parameters, the labels and the processors' settings are device data, not part of the key)
+               self._kv_format_key(cache), self._mode)  # (the mode: sampled, scored or greedy -- which bookkeeping kernel was captured, its constants, and whether dl_logits_process runs in front of it; the sampling parameters, the labels and the processors' settings are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)
@@ -490,11 +501,11 @@ class DecodeScheduler:
         for _ in range(n_steps):
             g.replay()
 
-    def _first_token(self, st, x_last, min_new):
+    def _first_token(self, st, x_last):
         if st.use_gemv and x_last.dim() == 2 and x_last.is_contiguous():
             # up to three rows: the weight-streaming GEMV the decode steps use for the same matrix (41 vs 61 us for the library's skinny GEMM at B=1)
             ops.gemv(self.lm_head.weight, st.logits, x=x_last)
         else:
             torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
         self._prefill_logits_buf.copy_(st.logits)
-        self._bookkeep(st, None, min_new)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits
+        self._bookkeep(st, None)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits

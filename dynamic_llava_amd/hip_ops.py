@@ -858,16 +858,24 @@ def gemv_gu_tp_any(w, *args, **kw):
     return _wrapper_for(w, "gemv_gu_tp", "gemv_gu_tp_pk")(w, *args, **kw)
 
 
+def _eos_set(eos_id, entry):
+    """eos_id: -1 (none), one id, or a sequence of up to three ids (the EOS set) -> the three ids the step-closing entries take (-1: unused)."""
+    eos = [int(e) for e in eos_id] if isinstance(eos_id, (list, tuple)) else [int(eos_id)]
+    if len(eos) > 3:
+        raise HipOpsError(f"{entry} compares at most three eos ids on the device")
+    return (eos + [-1, -1, -1])[:3]
+
+
+def _step_shapes(logits, next_ids, out_ids):  # what the step-closing entries ask of their logits [B, V] (any row stride) and of next_ids -> (B, V, out_cap)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
+    return (*logits.shape, out_ids.shape[1] if out_ids is not None else 0)
+
+
 def decode_advance(logits, next_ids, out_ids=None, step=None, finished=None, eos_id=-1, pad_id=0, kv_len_full=None, kv_len_sparse=None, decision=None, min_new_tokens=0):
     """eos_id: -1 (none), one id, or a sequence of up to three ids (the EOS set)."""
     _dev(logits, next_ids)
-    eos = [int(e) for e in eos_id] if isinstance(eos_id, (list, tuple)) else [int(eos_id)]
-    if len(eos) > 3:
-        raise HipOpsError("dl_decode_advance compares at most three eos ids on the device")
-    eos = (eos + [-1, -1, -1])[:3]
-    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
-    B, V = logits.shape
-    out_cap = out_ids.shape[1] if out_ids is not None else 0
+    eos = _eos_set(eos_id, "dl_decode_advance")
+    B, V, out_cap = _step_shapes(logits, next_ids, out_ids)
     _check(
         lib().dl_decode_advance(
             _p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(next_ids), _p(out_ids), out_cap, _p(step), _p(finished), eos[0], eos[1], eos[2], int(pad_id),
@@ -901,18 +909,13 @@ def decode_sample(logits, next_ids, params, out_ids=None, step=None, finished=No
                   kept_mask=None):
     """dl_decode_advance's bookkeeping around a sampled token (include/dynllava.h, sampling.py).  params: int32 [8] DEVICE tensor holding a dl_sample_params;
     kept_mask: optional uint8 [B, V] debug output (1 = token in the kept set)."""
-    eos = [int(e) for e in eos_id] if isinstance(eos_id, (list, tuple)) else [int(eos_id)]
-    if len(eos) > 3:
-        raise HipOpsError("dl_decode_sample compares at most three eos ids on the device")
-    eos = (eos + [-1, -1, -1])[:3]
+    eos = _eos_set(eos_id, "dl_decode_sample")
     _dev(logits, next_ids, params, kept_mask)
-    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
-    B, V = logits.shape
+    B, V, out_cap = _step_shapes(logits, next_ids, out_ids)
     if params is not None:  # (None reaches the library, which refuses it)
         assert params.dtype == torch.int32 and params.numel() >= 8 and params.is_contiguous()
     if kept_mask is not None:
         assert kept_mask.dtype == torch.uint8 and kept_mask.shape == (B, V) and kept_mask.is_contiguous()
-    out_cap = out_ids.shape[1] if out_ids is not None else 0
     _check(
         lib().dl_decode_sample(
             _p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(next_ids), _p(out_ids), out_cap, _p(step), _p(finished), eos[0], eos[1], eos[2], int(pad_id),
@@ -927,8 +930,7 @@ def decode_score(logits, next_ids, labels, nll, top1=None, out_ids=None, step=No
     """dl_decode_advance's bookkeeping around a LABEL, scored (include/dynllava.h, scoring.py).  labels: int64 [B, label_cap] DEVICE tensor (an entry outside
     [0, V) means "no label": the row is exhausted); nll: fp32 [B, label_cap]; top1: optional int64 [B, label_cap].  Slot step[b] of a live row is written."""
     _dev(logits, next_ids, labels, nll, top1)
-    assert logits.dim() == 2 and logits.stride(1) == 1 and next_ids.dtype == torch.int64
-    B, V = logits.shape
+    B, V, out_cap = _step_shapes(logits, next_ids, out_ids)
     label_cap = 0
     if labels is not None:  # (None reaches the library, which refuses it)
         assert labels.dtype == torch.int64 and labels.dim() == 2 and labels.shape[0] == B and labels.is_contiguous()
@@ -938,7 +940,6 @@ def decode_score(logits, next_ids, labels, nll, top1=None, out_ids=None, step=No
         label_cap = label_cap or nll.shape[1]
     if top1 is not None:
         assert top1.dtype == torch.int64 and top1.is_contiguous() and top1.shape == (B, label_cap)
-    out_cap = out_ids.shape[1] if out_ids is not None else 0
     _check(
         lib().dl_decode_score(
             _p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(labels), int(label_cap), _p(nll), _p(top1), _p(next_ids), _p(out_ids), out_cap, _p(step), _p(finished),

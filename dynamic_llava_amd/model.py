@@ -37,7 +37,7 @@ from . import logits_rules, sampling, scoring
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
-from .decode import DecodeScheduler, _DecodeState, no_gc_during_capture  # noqa: F401
+from .decode import DecodeScheduler, StepMode, _DecodeState, no_gc_during_capture  # noqa: F401
 from .modules import (CLIPVisionTower, CausalLMOutputWithPast, DynamicLlamaDecoderLayer, DynamicLlavaLlamaModel, TextPredictor,  # noqa: F401 (re-exported:
                       VisionPredictor)  # tests, tools and the package's lazy attributes import these names from here)
 from .prefill import USER_IDS, PrefillEngine  # noqa: F401
@@ -57,6 +57,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._packed = False
         self._rope = None
         self._dstate = None
+        self._mode = StepMode()
         self._prefill_graphs = {}
         self._prefill_pool = None
         # captured prefill shapes kept (LRU).  288 GB of HBM: the graphs share one memory pool, an entry costs its static inputs (~0.7 MB of
@@ -471,7 +472,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             cache.ensure_capacity(2)
             self._rope_tables(max(cache.full_len_host) + 2)
             st.cur_ids.copy_(input_ids[:, 0])
-            self._eos, self._pad = -1, 0
+            self._mode = StepMode()
             # the decode schedule (KVSlabCache.sched_*): the same rule generate() follows, evaluated step by step -- a forward()-driven loop
             # replays the same kernels as generate() on the same request.  Costs one device->host copy of the lengths per CHUNK of steps
             if self.decode_sync_every <= 0:
@@ -800,18 +801,15 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             st.qa_gran.zero_()  # and of dl_gemv_qkv_attn
         if st.tp_gran is not None:
             st.tp_gran.zero_()  # and of dl_gemv_gu_tp
-        self._eos = -1 if eos is None else (tuple(eos) if isinstance(eos, list) else eos)  # one id or a tuple of up to three (the EOS set)
-        self._pad = pad
-        self._min_new = min_new
-        self._sampled = sampled is not None  # which bookkeeping kernel _first_token / the decode steps launch (and capture)
+        forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
+        # which bookkeeping kernel _first_token / the decode steps launch (and capture), and what it is told
+        self._mode = StepMode(eos=-1 if eos is None else (tuple(eos) if isinstance(eos, list) else eos), pad=pad, min_new=min_new, sampled=sampled is not None,
+                              forced=forced is not None, processed=rules.on)
         if sampled is not None:
             st.sample_params.copy_(ops.sample_params_words(*sampled))
-        self._processed = rules.on  # dl_logits_process in front of the bookkeeping kernel (launched, and captured); an all-neutral request is exactly the request without the keywords
         if rules.on:  # the settings are device data like the sampling parameters: one graph serves every penalty, n-gram size and word list
             st.logits_params.copy_(ops.logits_params_words(rules.repetition_penalty, rules.no_repeat_ngram_size, len(rules.bad_words)))
             st.bad_words.copy_(ops.bad_words_table(rules.bad_words, "cpu"))
-        forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
-        self._forced = forced is not None  # dl_decode_score in the place of dl_decode_advance: score the label, feed the label
         if forced is not None:
             st.labels.fill_(scoring.IGNORE)
             st.labels[:, : forced.shape[1]].copy_(forced)
@@ -828,8 +826,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             # equally long multi-turn prompts whose last "USER:" sits elsewhere must not share a graph
             li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
             key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
-                   cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._eos, self._pad, min_new, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key(), self._kv_format_key(cache), self._sampled, self._forced, self._processed)  # (a knob toggled at run time must not replay a graph captured under the other setting)
+                   cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._mode, repr(self.config.sparse_config), li_key,
+                   self._prefill_knob_key(), self._kv_format_key(cache))  # (a knob toggled at run time must not replay a graph captured under the other setting)
             ent = self._prefill_graphs.get(key)
             if ent is None:
                 # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
@@ -850,7 +848,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 else:
                     ent["didx"] = self._dev_idx(lay)
 
-                def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, min_new=min_new, cache=cache, st=st):
+                def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st):
                     if dev_layout:
                         p_ = ent["plan"]  # the plan's shapes are the bucket's; its device metadata is (re)written here at the true width
                         ops.prompt_layout_into(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS, ent["didx"], w_true=ent["w_true"], n_drop=(p_["n_img"] - p_["k"]) if p_["vision_on"] else 0,
@@ -858,7 +856,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                     f = ent["feats"] if ent["feats"] is not None else (self.encode_images(ent["images"]) if ent["images"] is not None else None)
                     emb = self._assemble(lay, ent["didx"], ent["ids"], f)
                     x = self._prefill_run(ent["plan"], emb, cache, copy.deepcopy(ent["indices"]), True)
-                    self._first_token(st, x, min_new)
+                    self._first_token(st, x)
 
                 ent["run"] = run
                 self._prefill_graphs[key] = ent
@@ -902,20 +900,20 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             f = image_features if image_features is not None else (self.encode_images(images) if images is not None else None)
             embeds = self._assemble(lay, self._dev_idx(lay), inputs, f)
             x, cache, _, _ = self._prefill(embeds, lens, indices, cache, reserve=max_new + 1, last_only=True)
-            self._first_token(st, x, min_new)
+            self._first_token(st, x)
         self.last_prefill_logits = self._prefill_logits_buf
         if tm is not None:
             tm["ev"][1].record()
             tm["path"] = prefill_path
         scores, raw_logits = [], []
 
-        eos_ids = [] if self._eos == -1 else (list(self._eos) if isinstance(self._eos, tuple) else [self._eos])
+        eos_ids = [] if self._mode.eos == -1 else (list(self._mode.eos) if isinstance(self._mode.eos, tuple) else [self._mode.eos])
 
         def _score(step_idx):  # HF `scores`: the processed logits of that step (EOS at -inf while step < min_new_tokens)
             z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
             if want_logits:
                 raw_logits.append(z.clone())
-            if self._processed:  # what dl_logits_process left for this step's bookkeeping launch (the buffer is read after every step on this route)
+            if self._mode.processed:  # what dl_logits_process left for this step's bookkeeping launch (the buffer is read after every step on this route)
                 z = st.proc_logits.clone()
             if sampled is not None:  # the processed logits of a sampled step: z = logit / T with -inf outside the kept set (sampling.py), as HF reports them
                 # (on the host side of the loop, with the contract's own arithmetic: this branch reads the step buffer after every step anyway)
@@ -945,7 +943,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 st.obs_ev[slot].synchronize()
                 row = st.obs_host[slot]
                 cache.sched_observe(at, int(row[B : 2 * B].max()))
-                if (eos_ids or self._forced) and int(row[2 * B :].min()) != 0:  # (score(): finished = labels exhausted)
+                if (eos_ids or self._mode.forced) and int(row[2 * B :].min()) != 0:  # (score(): finished = labels exhausted)
                     all_done = True
             if all_done:
                 break
@@ -962,7 +960,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             if produced < max_new:
                 slot = chunks % 4
                 st.obs_host[slot, : 2 * B].copy_(cache.lens.view(-1), non_blocking=True)
-                if eos_ids or self._forced:
+                if eos_ids or self._mode.forced:
                     st.obs_host[slot, 2 * B :].copy_(st.finished, non_blocking=True)
                 st.obs_ev[slot].record()
                 pending.append((slot, produced))

@@ -680,18 +680,18 @@ TABLES = {"text_predictor": (TP_TABLE, run_tp), "gemv_gu_tp": (GU_TABLE, run_gu_
 # the branches, read out of the sources
 # ------------------------------------------------------------------------------------------------------------------------------
 def branches_in_sources(csrc):
-    """The thresholds the shapes above were chosen for, parsed out of csrc/tp_body.h, predictors.hip and gemv.hip; AssertionError when one is no longer
+    """The thresholds the shapes above were chosen for, parsed out of csrc/tp_body.h, predictors.hip, advance.hip and gemv.hip; AssertionError when one is no longer
     written as restated here."""
     read = lambda name: open(os.path.join(csrc, name)).read()
-    tp, pr, gv = read("tp_body.h"), read("predictors.hip"), read("gemv.hip")
+    tp, pr, adv, gv = read("tp_body.h"), read("predictors.hip"), read("advance.hip"), read("gemv.hip")
     out = dict(max_chunks=int(re.search(r"constexpr int kTp1MaxChunks = (\d+);", tp).group(1)), pb=int(re.search(r"constexpr int PB = (\d+);", tp).group(1)))
     assert "const bool pre = nvec <= 64 * MAXC;" in tp
     m = re.search(r"const bool pre = K5 % V == 0 && K5 / V <= (\d+) && passes <= (\d+);", tp)
     out["k5_vecs"], out["max_passes"] = int(m.group(1)), int(m.group(2))
     assert "const int passes = (N5 + nw * 4 - 1) / (nw * 4);" in tp and "dim3(512), (size_t)(D / 2 + D / 4 + 2) * sizeof(float)" in pr  # 8 waves: 32 neurons a pass
-    m = re.search(r"for \(int c0 = 0; c0 < n_chunks; c0 \+= (\d+) \* (\d+)\)", pr)
+    m = re.search(r"for \(int c0 = 0; c0 < n_chunks; c0 \+= (\d+) \* (\d+)\)", adv)
     out["trip_chunks"] = int(m.group(1)) * int(m.group(2))
-    assert "(row_stride % VE == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0)" in pr
+    assert "(row_stride % VE == 0) && ((reinterpret_cast<uintptr_t>(logits) & 15) == 0)" in adv
     out["h_max"] = int(re.search(r"DL_REQUIRE\(H <= (\d+), \"dl_text_predictor_decide", pr).group(1))
     m = re.search(r"if \(a\.K / Elem<T>::kVec <= 64 \* (\d+)\) hipLaunchKernelGGL\(\(gemv_gu_tp_kernel<T, (\d+), PK>\).*\n\s*else hipLaunchKernelGGL\(\(gemv_gu_tp_kernel<T, (\d+), PK>\)", gv)
     assert m and m.group(1) == m.group(2)

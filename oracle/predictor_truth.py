@@ -1,6 +1,6 @@
 """Truth and the acceptance criterion for the code that takes the model's discrete decisions: the text predictor (csrc/tp_body.h, three launches or extra
 workgroups of dl_gemv_gu_tp), the small kernels of the vision predictor (csrc/predictors.hip: vp_build_index, vp_pool_concat, vp_head) and the greedy
-advance (dl_decode_advance).  docs/predictor_exactness.md has the construction, the mutant table and the measured figures.
+advance (dl_decode_advance: csrc/advance.hip, closing the step by csrc/step_close.h).  docs/predictor_exactness.md has the construction, the mutant table and the measured figures.
 
 Every stage is judged from the kernel's OWN previous intermediate (h1 / a1 in the caller's workspace, the vision predictor's workspace regions), so the error
 of one stage never widens the set of the next.

@@ -206,12 +206,12 @@ def test_one_graph_serves_every_setting_and_off_stays_off():
     # an all-neutral request is the request without the keywords: same graphs, same tokens
     assert torch.equal(model.generate(**kw, repetition_penalty=1.0, no_repeat_ngram_size=0, bad_words_ids=[]), plain)
     assert torch.equal(model.generate(**kw, repetition_penalty=None, no_repeat_ngram_size=None, bad_words_ids=None), plain)
-    assert len(st.graphs) == n_dec and len(model._prefill_graphs) == n_pre and model._dstate is st and model._processed is False
+    assert len(st.graphs) == n_dec and len(model._prefill_graphs) == n_pre and model._dstate is st and model._mode.processed is False
     words = _bad_words(plain)
     for _ in range(3):
         first = model.generate(**kw, **PROC, bad_words_ids=words)
     n_dec2, n_pre2 = len(st.graphs), len(model._prefill_graphs)
-    assert n_dec2 > n_dec and n_pre2 == n_pre + 1 and model._processed is True
+    assert n_dec2 > n_dec and n_pre2 == n_pre + 1 and model._mode.processed is True
     outs = [first]
     for pk in (dict(repetition_penalty=0.7), dict(no_repeat_ngram_size=1), dict(repetition_penalty=2.0, no_repeat_ngram_size=3, bad_words_ids=[[5], [6, 7, 8]]),
                dict(bad_words_ids=[[int(plain[0, 0])]])):

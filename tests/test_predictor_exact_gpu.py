@@ -4,7 +4,7 @@ tests/test_kernels_gpu.py bounds max|err| of the predictors' logits over the who
 tests/test_predictor_truth_cpu.py shows a dropped 16-byte chunk, a neighbour's bias, a missing rounding and a `>=` in the decision passing that.  Here every
 stage is judged from the kernel's own previous intermediate (the caller's workspace) against the set of values its specification can produce
 (oracle/predictor_truth.py), on integer-lattice inputs whose every element has one feasible value and on generic rows with planted logit gaps, at the
-smallest shapes that reach each branch of csrc/tp_body.h and csrc/predictors.hip (oracle/predictor_cases.py: the tables and the runner) -- inside guard
+smallest shapes that reach each branch of csrc/tp_body.h, csrc/predictors.hip and csrc/advance.hip (oracle/predictor_cases.py: the tables and the runner) -- inside guard
 bands, every launch twice with the same bits.  dl_decode_advance is compared bit for bit with a plain restatement.  docs/predictor_exactness.md has the
 construction, the mutant table and the measured results."""
 import pytest

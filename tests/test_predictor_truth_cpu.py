@@ -1,7 +1,7 @@
 """CPU: the standard behind tests/test_predictor_exact_gpu.py discriminates, and reaches every branch it was built for.
 
   * the premises of the lattice class and the measured constant are re-derived here;
-  * the thresholds of csrc/tp_body.h, csrc/predictors.hip and csrc/gemv.hip are parsed out of the sources, and every branch they open has a table entry;
+  * the thresholds of csrc/tp_body.h, csrc/predictors.hip, csrc/advance.hip and csrc/gemv.hip are parsed out of the sources, and every branch they open has a table entry;
   * every runner of oracle/predictor_cases.py is dry-run on the documented arithmetic in a summation order of no kernel (EmuAdaptor): zero elements outside;
   * each mutant of docs/predictor_exactness.md puts at least one element outside on the class the document names;
   * the same mutants are put through the assertions of tests/test_kernels_gpu.py on its shapes (the table of the document)."""
