@@ -30,6 +30,7 @@ class StepMode:
     sampled: bool = False  # dl_decode_sample: generate(do_sample=True, seed=...)
     forced: bool = False  # dl_decode_score: score() -- score the label, feed the label
     processed: bool = False  # dl_logits_process in front of the kernel; an all-neutral request is exactly the request without the keywords
+    logprobs: int = -1  # dl_decode_logprobs behind the kernel: generate(output_logprobs=True, top_logprobs=n) -- -1: off, else n
 
 
 class _DecodeState:
@@ -103,6 +104,9 @@ class _DecodeState:
         self.proc_logits = torch.empty((B, V), dtype=torch.float32, device=device)
         self.logits_params = ops.logits_params_block(device)
         self.bad_words = ops.bad_words_table((), device)
+        # dl_decode_logprobs' outputs (generate(output_logprobs=True)): made by need_logprobs() on the first such request -- a model that never asks keeps its
+        # footprint -- and with the state thereafter; slot j belongs to step j, like out_ids
+        self.lp = self.top_lp = self.top_ids = None
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
         self.tp_gran = ops.gemv_gu_tp_workspace(tpm.d_model, device) if (B == 1 and tpm is not None and dtype in (torch.bfloat16, torch.float16) and H <= 5120 and H % 8 == 0 and tpm.d_model % 32 == 0) else None
@@ -114,6 +118,17 @@ class _DecodeState:
         self.obs_host = torch.empty((4, 3 * B), dtype=torch.int32).pin_memory()
         self.obs_ev = [torch.cuda.Event() for _ in range(4)]
         self.n_cu = torch.cuda.get_device_properties(device).multi_processor_count
+
+
+    def need_logprobs(self):
+        """Allocates the log-probability buffers once per state (the captured launches hold their pointers)."""
+        if self.lp is None:
+            from .logprobs import MAX_TOP_LOGPROBS
+
+            B, cap, dev = *self.out_ids.shape, self.out_ids.device
+            self.lp = torch.zeros((B, cap), dtype=torch.float32, device=dev)
+            self.top_lp = torch.zeros((B, cap, MAX_TOP_LOGPROBS), dtype=torch.float32, device=dev)
+            self.top_ids = torch.full((B, cap, MAX_TOP_LOGPROBS), -1, dtype=torch.int64, device=dev)
 
 
 @contextlib.contextmanager
@@ -178,6 +193,8 @@ class DecodeScheduler:
             ops.decode_sample(logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
         else:  # EOS is banned while step < min_new (HF semantics)
             ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
+        if m.logprobs >= 0:  # generate(output_logprobs=True): the committed token's log-probability on the step's RAW logits (slot step - 1)
+            ops.decode_logprobs(st.logits, st.cur_ids, st.step, st.lp, m.logprobs, st.top_lp, st.top_ids)
 
     def _use_tp(self):
         """The output text predictor decides in the decode step (it sits in front of a layer that exists)."""
@@ -487,7 +504,8 @@ class DecodeScheduler:
             return
         g = st.graphs.get(key)
         if g is None:
-            # the warm-up executes one real step: snapshot / restore the state it advances
+            # the warm-up executes one real step: snapshot / restore the state it advances.  (dl_decode_logprobs' outputs need no entry: the warm-up writes slot
+            # `step` of st.lp / top_lp / top_ids from the logits of this very step, and the first replay below, back at the same `step`, writes that slot again)
             snap = (st.cur_ids.clone(), st.out_ids.clone(), st.step.clone(), st.finished.clone(), cache.lens.clone(), st.decision.clone())
 
             def warm():

@@ -170,6 +170,7 @@ SIGNATURES = {
         [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "dl_logits_process": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dl_decode_logprobs": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -948,6 +949,34 @@ def decode_score(logits, next_ids, labels, nll, top1=None, out_ids=None, step=No
         "dl_decode_score",
     )
     return next_ids
+
+
+def decode_logprobs(logits, next_ids, step, logprobs, n_top=0, top_logprobs=None, top_ids=None):
+    """The log-probability of the token the step-closing launch has just committed, and the step's n_top most probable tokens (include/dynllava.h, logprobs.py):
+    runs after decode_advance / decode_sample on the step's RAW logits [B, V] (any row stride).  next_ids int64 [B], step int32 [B]: as that launch left them;
+    logprobs fp32 [B, cap]; top_logprobs fp32 / top_ids int64 [B, cap, >= n_top] (None with n_top = 0).  Slot step[b] - 1 of a row is written when it lies in
+    [0, cap), nothing else."""
+    _dev(logits, next_ids, step, logprobs, top_logprobs, top_ids)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    cap, top_stride = 0, 0
+    if next_ids is not None:  # (None reaches the library, which refuses it)
+        assert next_ids.dtype == torch.int64 and next_ids.numel() == B and next_ids.is_contiguous()
+    if step is not None:
+        assert step.dtype == torch.int32 and step.numel() == B and step.is_contiguous()
+    if logprobs is not None:
+        assert logprobs.dtype == torch.float32 and logprobs.dim() == 2 and logprobs.shape[0] == B and logprobs.is_contiguous()
+        cap = logprobs.shape[1]
+    if top_logprobs is not None or top_ids is not None:
+        assert top_logprobs is not None and top_ids is not None and top_logprobs.dtype == torch.float32 and top_ids.dtype == torch.int64
+        assert top_logprobs.dim() == 3 and top_logprobs.shape[:2] == (B, cap) and top_ids.shape == top_logprobs.shape and top_logprobs.is_contiguous() and top_ids.is_contiguous()
+        top_stride = top_logprobs.shape[2]
+    _check(
+        lib().dl_decode_logprobs(_p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(next_ids), _p(step), int(cap), _p(logprobs), int(n_top), int(top_stride),
+                                 _p(top_logprobs), _p(top_ids), _stream()),
+        "dl_decode_logprobs",
+    )
+    return logprobs
 
 
 def logits_params_words(repetition_penalty=1.0, no_repeat_ngram_size=0, n_bad_words=0):

@@ -33,7 +33,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import logits_rules, sampling, scoring
+from . import logits_rules, logprobs, sampling, scoring
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -427,6 +427,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "decode_weight_format": self.decode_weight_format, "mx8_max_decode_batch": self.mx8_max_decode_batch, "kv_cache_format": self.kv_cache_format,
             "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
             "device_logits_processors": True,  # repetition_penalty / no_repeat_ngram_size / bad_words_ids act inside the captured graphs (dl_logits_process)
+            "device_logprobs": True,  # generate(output_logprobs=True, top_logprobs=n) reads the log-probabilities off inside the captured graphs (dl_decode_logprobs)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }
@@ -566,8 +567,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         TopKLogitsWarper, TopPLogitsWarper: the smallest set of most probable tokens whose mass reaches top_p is kept), drawn with
         torch's generator -- a plain loop over forward() (no hipGraph: this is the convenience path, the harness default is greedy).
         Token streams cannot match HF's draw for draw (different RNG consumption); the distribution per step is the same.
-        repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call."""
+        repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call.
+        output_logprobs / top_logprobs: logprobs.reference_rows on every step's raw fp32 logits (the rule dl_decode_logprobs implements), masked behind a row's EOS."""
         rules = self._logits_rules(kwargs)
+        n_lp = logprobs.validate(kwargs, self.config.vocab_size)
         temperature = float(kwargs.get("temperature", 1.0) or 1.0)
         top_k = int(kwargs.get("top_k", 0) or 0)
         top_p = kwargs.get("top_p")
@@ -583,9 +586,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self.last_prefill_logits = logits.float().clone()
         B = logits.shape[0]
         finished = torch.zeros(B, dtype=torch.bool, device=self.device)
-        toks, scores = [], []
+        toks, scores, raw = [], [], []
         for step in range(max_new):
             z = logits.float()
+            if n_lp >= 0:
+                raw.append(z.clone())  # the model's own distribution: before the processors, the EOS ban and the warpers
             if rules.on:
                 z = rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
             z = z / temperature
@@ -618,6 +623,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             res = {"sequences": seq, "past_key_values": cache}
             if kwargs.get("output_scores"):
                 res["scores"] = tuple(scores)
+            if n_lp >= 0:
+                res.update(logprobs.host_result(raw, seq, eos_set, n_lp))
             return res
         return seq
 
@@ -631,6 +638,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         tokens through single decode steps; plain loop over forward(), no hipGraph.  repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process
         on every step's logits, on the tokens emitted in this call."""
         rules = self._logits_rules(kwargs)
+        n_lp = logprobs.validate(kwargs, self.config.vocab_size)
         if images is not None or kwargs.get("image_features") is not None:
             raise NotImplementedError("generate(past_key_values=...) continues a dialogue: the image belongs to the first call")
         cache = kwargs["past_key_values"]
@@ -656,8 +664,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         logits = out.logits[:, -1].float()
         self.last_prefill_logits = logits.clone()
         finished = torch.zeros(inputs.shape[0], dtype=torch.bool, device=self.device)
-        toks, scores = [], []
+        toks, scores, raw = [], [], []
         for step in range(max_new):
+            if n_lp >= 0:
+                raw.append(logits.clone())  # the model's own distribution: before the processors and the EOS ban
             z = rules.apply(logits, torch.stack(toks, dim=1) if toks else [[]] * inputs.shape[0]) if rules.on else logits.clone()
             if step < min_new and eos_set:
                 z[:, eos_set] = float("-inf")
@@ -679,6 +689,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             res = {"sequences": seq, "past_key_values": cache}
             if kwargs.get("output_scores"):
                 res["scores"] = tuple(scores)
+            if n_lp >= 0:
+                res.update(logprobs.host_result(raw, seq, eos_set, n_lp))
             return res
         return seq
 
@@ -726,6 +738,13 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         graphs (dl_logits_process; the rule is logits_rules.py), in front of the EOS ban of min_new_tokens and of temperature / top_k / top_p; a request past
         logits_rules.MAX_NGRAM / MAX_BAD_WORDS / MAX_BAD_WORD_LEN runs the plain loop over forward() with the same rule; `scores` are the processed logits,
         `logits` the raw ones).  Bad values of these raise ValueError before any launch.
+        output_logprobs=True (with return_dict_in_generate=True) adds `logprobs`: fp32 [B, T], the log-probability of sequences[b, t]; top_logprobs=n (an int in
+        0..logprobs.MAX_TOP_LOGPROBS, default 0) adds `top_logprobs` fp32 [B, T, n] and `top_logprob_ids` int64 [B, T, n], the step's n most probable tokens (logit
+        descending, index ascending).  The distribution is always that of the model's OWN step logits -- the raw ones output_logits=True reports, the quantity score()
+        uses -- before the logits processors, before the EOS ban of min_new_tokens and before temperature / top_k / top_p, also for a sampled token.  Read off on the
+        device inside the same captured graphs (dl_decode_logprobs behind the step-closing launch; the rule is logprobs.py): no [B, V] tensor reaches the host and
+        the decode loop keeps its chunks.  Columns after a row's first EOS (pad in `sequences`) hold 0.0 / -1, the EOS token's own entry is real; the host routes
+        (_generate_sample, _generate_on_cache) return the same keys from the same rule.  Bad values raise ValueError before any launch.
         Still ignored without a word: streamer, stopping_criteria, logits_processor, suppress_tokens, sequence_bias.
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
@@ -734,6 +753,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         rules = self._logits_rules(kwargs)  # validated here, before any launch
         if rules.on and kwargs.get("_score_labels") is not None:
             raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
+        n_lp = logprobs.validate(kwargs, self.config.vocab_size)  # -1: not asked for; else the number of alternatives per step
         sampled = None  # (temperature, top_k, top_p, seed, row base) when the device sampler draws the tokens
         if kwargs.get("do_sample", False):  # model_vqa_loader.py:162-175 passes do_sample = temperature > 0 (default 0: greedy)
             if "inputs_embeds" in kwargs:
@@ -804,7 +824,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
         # which bookkeeping kernel _first_token / the decode steps launch (and capture), and what it is told
         self._mode = StepMode(eos=-1 if eos is None else (tuple(eos) if isinstance(eos, list) else eos), pad=pad, min_new=min_new, sampled=sampled is not None,
-                              forced=forced is not None, processed=rules.on)
+                              forced=forced is not None, processed=rules.on, logprobs=n_lp)
         if sampled is not None:
             st.sample_params.copy_(ops.sample_params_words(*sampled))
         if rules.on:  # the settings are device data like the sampling parameters: one graph serves every penalty, n-gram size and word list
@@ -815,6 +835,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             st.labels[:, : forced.shape[1]].copy_(forced)
             st.nll.zero_()
             st.top1.fill_(-1)
+        if n_lp >= 0:  # dl_decode_logprobs' outputs: slots of this request that no launch reaches must not show an earlier request's values
+            st.need_logprobs()
+            st.lp.zero_(); st.top_lp.zero_(); st.top_ids.fill_(-1)
         if getattr(self, "_prefill_logits_buf", None) is None or self._prefill_logits_buf.shape != st.logits.shape:
             self._prefill_logits_buf = torch.empty(st.logits.shape, dtype=torch.float32, device=self.device)
         vp = getattr(self.model, "image_score_predictor", None)
@@ -1010,5 +1033,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 res["scores"] = tuple(scores)
             if want_logits:
                 res["logits"] = tuple(raw_logits)
+            if n_lp >= 0:  # the columns `sequences` kept; after a row's first EOS (pad in `sequences`) 0.0 / -1
+                W = out.shape[1]
+                lp, top_lp, top_ids = logprobs.mask_after_eos(out, eos_ids, st.lp[:, :W].clone(), st.top_lp[:, :W, :n_lp].clone(), st.top_ids[:, :W, :n_lp].clone())
+                res["logprobs"] = lp
+                if n_lp > 0:
+                    res["top_logprobs"], res["top_logprob_ids"] = top_lp, top_ids
             return res
         return out

@@ -481,6 +481,25 @@ int dl_logits_process(const void* logits, int logits_dtype, int64_t logits_row_s
                       float* out, const int64_t* out_ids, int out_cap, const int32_t* step,
                       const dl_logits_params* params, const int32_t* bad_words, void* stream);
 
+/* ---- log-probabilities of the tokens a generation picks (generate(output_logprobs=True, top_logprobs=n)): runs AFTER the step-closing launch
+ * (dl_decode_advance / dl_decode_sample) on the step's RAW logits -- the model's own distribution, before logits processors, the min_new_tokens EOS ban and
+ * temperature / top-k / top-p.  Per row b, with slot = step[b] - 1 (the slot the step-closing launch has just filled) and tok = next_ids[b] (the token it
+ * committed): nothing is written when slot < 0 or slot >= cap; otherwise logprobs[b, slot], top_logprobs[b, slot, :n_top] and top_ids[b, slot, :n_top] are
+ * written and nothing else.  `finished` is not read: what a finished row reports is masked by the host (logprobs.mask_after_eos).
+ * The rule, per row (dynamic_llava_amd/logprobs.py states it in full and is what the kernel is tested against):
+ *   1. m, mass_v, M and lse exactly as dl_decode_score's steps 1-5 above.
+ *   2. logprob(v) = -((m - x_v) + lse): two fp32 operations, then an exact negation -- the bit-exact negative of dl_decode_score's nll for the label v.
+ *      logprobs[b, slot] = logprob(tok); a tok outside [0, V) is never used as an index and reports 0.0.
+ *   3. top_ids[b, slot, :n_top] are the first n_top entries of the vocabulary ordered by (logit descending, index ascending), top_logprobs their logprob;
+ *      -inf logits take part in that order and report -inf.
+ * logits: bf16 / fp16 / fp32, any row stride, V <= 65536; next_ids: int64 [B]; step: int32 [B]; logprobs: float [B, cap]; 0 <= n_top <= 8, n_top <= V,
+ * n_top <= top_stride; top_logprobs: float [B, cap, top_stride] and top_ids: int64 [B, cap, top_stride] (both may be NULL when n_top == 0); DL_ERR_ARG
+ * otherwise.  One workgroup per row; no workspace, no global atomics, never synchronises: capturable. */
+#define DL_MAX_TOP_LOGPROBS 8
+int dl_decode_logprobs(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
+                       const int64_t* next_ids, const int32_t* step, int cap, float* logprobs,
+                       int n_top, int top_stride, float* top_logprobs, int64_t* top_ids, void* stream);
+
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
  * operand registers).  bf16 / f16, fp32 accumulate, one rounding.  K % 256 == 0, N % 4 == 0; ldx / ldy: row strides (elements).
