@@ -1,23 +1,16 @@
-"""Decode side of the engine: the persistent step state (stable pointers for the hipGraph), the three step builders (GEMV / small-M / library), the pooled KV slab, the schedule that picks a captured step from the observed lengths, device-error reporting.  A mixin of DynamicLlavaLlamaForCausalLM (model.py); split out in round 6 (no behaviour change)."""
+"""Decode side of the engine: the persistent step state (stable pointers for the hipGraph), the three step builders (GEMV / small-M / library), the pooled KV slab, the schedule that picks a captured step from the observed lengths, device-error reporting; of generate()'s stages, arming the state for a request (_bind_schedule, _arm) and the chunked decode loop (_decode_loop).  A mixin of DynamicLlavaLlamaForCausalLM (model.py)."""
 from __future__ import annotations
 
-
 import contextlib
-import copy
 import gc
-import math
-import os
 from dataclasses import dataclass
-from typing import List, Optional, Tuple
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
 from .cache import KVSlabCache, KVSlabCacheMX8
-from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
-
+from .config import IGNORE_INDEX
 
 
 @dataclass(frozen=True)
@@ -31,6 +24,12 @@ class StepMode:
     forced: bool = False  # dl_decode_score: score() -- score the label, feed the label
     processed: bool = False  # dl_logits_process in front of the kernel; an all-neutral request is exactly the request without the keywords
     logprobs: int = -1  # dl_decode_logprobs behind the kernel: generate(output_logprobs=True, top_logprobs=n) -- -1: off, else n
+
+    @classmethod
+    def of(cls, req, max_new):
+        """The mode of a parsed request (request.Request) of max_new steps; the one place the EOS tuple becomes the kernels' -1 / id / tuple."""
+        return cls(eos=-1 if not req.eos else (req.eos[0] if len(req.eos) == 1 else req.eos), pad=req.pad, min_new=min(req.min_new, max_new), sampled=req.sampled is not None,
+                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp)
 
 
 class _DecodeState:
@@ -119,6 +118,14 @@ class _DecodeState:
         self.obs_ev = [torch.cuda.Event() for _ in range(4)]
         self.n_cu = torch.cuda.get_device_properties(device).multi_processor_count
 
+    def clear_granules(self):
+        """The decode attention's in-kernel split merge validates its granules by tag = (position of the new token, layer): within a request positions only grow, but a slot left
+        by an EARLIER REQUEST (or another cache, in a forward() loop) at the same position would match.  Tag 0 is never expected: one clear makes every older granule unmatchable."""
+        self.attn_ws.zero_()
+        if self.qa_gran is not None:
+            self.qa_gran.zero_()  # and of dl_gemv_qkv_attn
+        if self.tp_gran is not None:
+            self.tp_gran.zero_()  # and of dl_gemv_gu_tp
 
     def need_logprobs(self):
         """Allocates the log-probability buffers once per state (the captured launches hold their pointers)."""
@@ -431,14 +438,10 @@ class DecodeScheduler:
             # slots are allocated in steps of 128: a stream of requests of slightly different lengths (VQAL:123-196) keeps ONE slab -- and with it
             # every captured graph that holds pointers into it -- instead of re-allocating whenever a prompt is a few tokens longer than any before
             old_ptr = None if c is None else c.slab.data_ptr()
-            c = None
-            self._cache_pool = None
-            c = self._new_cache(B, -(-int(t_need) // 128) * 128)
-            self._cache_pool = c
+            c = self._cache_pool = None  # (the old slab goes before the new one comes)
+            c = self._cache_pool = self._new_cache(B, -(-int(t_need) // 128) * 128)
             if old_ptr is not None:  # graphs captured on the slab that has just been freed can never be replayed again
-                self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if old_ptr not in k}
-                if self._dstate is not None:
-                    self._dstate.graphs = {k: v for k, v in self._dstate.graphs.items() if old_ptr not in k}
+                self._drop_graphs_on(old_ptr)
         c.lens.zero_()
         c.full_len_host = [0] * B
         c.seen_tokens = 0
@@ -446,6 +449,38 @@ class DecodeScheduler:
         c.sparse_cap = c.logical_cap
         c.set_bounds(None, None)
         return c
+
+    def _drop_graphs_on(self, ptr):
+        """Forget every captured prefill and decode step whose key holds the slab pointer `ptr`: the slab was freed, or handed to a caller who may free it."""
+        self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if ptr not in k}
+        if self._dstate is not None:
+            self._dstate.graphs = {k: v for k, v in self._dstate.graphs.items() if ptr not in k}
+
+    def _bind_schedule(self, st, cache):
+        """The thresholds cache.n_splits / fused_attn_splits schedule this cache's decode steps by: this model's, for this state."""
+        (cache.single_split_max_keys, cache.fused_single_keys), cache.min_keys_per_split = self._single_split_max_keys(st), self.min_keys_per_split
+
+    def _arm(self, st, req, max_new):
+        """Readies the persistent state for a request (request.Request) of max_new steps, outside any graph.  What it sets beyond the mode -- sampling parameters,
+        the processors' settings and word list, score()'s labels -- is device data the captured launches read: one graph serves every value of them."""
+        st.step.zero_(); st.finished.zero_(); st.decision.fill_(1)
+        st.clear_granules()
+        self._mode = StepMode.of(req, max_new)  # which bookkeeping kernel _first_token / the decode steps launch (and capture), and what it is told
+        if req.sampled is not None:
+            st.sample_params.copy_(ops.sample_params_words(*req.sampled))
+        if req.rules.on:
+            st.logits_params.copy_(ops.logits_params_words(req.rules.repetition_penalty, req.rules.no_repeat_ngram_size, len(req.rules.bad_words)))
+            st.bad_words.copy_(ops.bad_words_table(req.rules.bad_words, "cpu"))
+        if req.forced is not None:
+            st.labels.fill_(IGNORE_INDEX)
+            st.labels[:, : req.forced.shape[1]].copy_(req.forced)
+            st.nll.zero_()
+            st.top1.fill_(-1)
+        if req.n_lp >= 0:  # dl_decode_logprobs' outputs: slots of this request that no launch reaches must not show an earlier request's values
+            st.need_logprobs()
+            st.lp.zero_(); st.top_lp.zero_(); st.top_ids.fill_(-1)
+        if getattr(self, "_prefill_logits_buf", None) is None or self._prefill_logits_buf.shape != st.logits.shape:
+            self._prefill_logits_buf = torch.empty(st.logits.shape, dtype=torch.float32, device=self.device)
 
     def _single_split_max_keys(self, st):
         """-> (largest row, in keys, that the fused q|k|v + attention launch takes; largest row it takes with ONE attention workgroup per head).
@@ -527,3 +562,46 @@ class DecodeScheduler:
             torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
         self._prefill_logits_buf.copy_(st.logits)
         self._bookkeep(st, None)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits
+
+    def _decode_loop(self, st, cache, max_new, sync_every, on_step=None):
+        """generate()'s decode loop behind the first token: chunks of captured steps, scheduled from the lengths the predictor actually leaves (DML:2377-2391,
+        CU:153-164) -> the number of tokens produced (the first included).  on_step(j), when given, runs after step j: the steps are then enqueued one by one
+        (the caller reads the step buffer after each); the schedule (chunks, bounds) is the same.  Before a chunk the host knows the un-evicted group's length
+        exactly, and the evicted group's as OBSERVED after an earlier chunk (non-blocking copy into pinned memory, consumed one chunk late so that the host never
+        waits for steps it has just enqueued) plus the steps enqueued since.  Those bounds pick the split-KV factor / the fused q|k|v+attention launch
+        (cache.n_splits), i.e. which captured graph is replayed; the values are data, never timing, so the schedule is deterministic for a given request."""
+        B, has_eos = st.B, self._mode.eos != -1
+        stops = has_eos or self._mode.forced  # (score(): finished = labels exhausted)
+        produced, chunks, pending = 1, 0, []  # pending: (ring slot, produced-when-copied)
+        cache.sched_begin(max(cache.full_len_host), getattr(cache, "prefill_sparse_max", None) or max(cache.full_len_host), sync_every)
+        while produced < max_new:
+            # EOS of a short answer (VQA: a few tokens) must not cost two chunks of wasted steps: the first chunks' flags are read blocking (one
+            # ~50 us queue drain each), later ones one chunk late.  The SCHEDULE never uses an observation newer than one chunk old either way.
+            keep_newest = 0 if (has_eos and chunks <= 2) else 1
+            all_done = False
+            while len(pending) > keep_newest:
+                slot, at = pending.pop(0)
+                st.obs_ev[slot].synchronize()
+                row = st.obs_host[slot]
+                cache.sched_observe(at, int(row[B : 2 * B].max()))
+                all_done = all_done or (stops and int(row[2 * B :].min()) != 0)
+            if all_done:
+                break
+            n = min(cache.sched_chunk(), max_new - produced)
+            if on_step is None:
+                self._run_decode_steps(st, cache, n)
+            else:
+                for i in range(n):
+                    self._run_decode_steps(st, cache, 1)
+                    on_step(produced + i)
+            produced += n
+            chunks += 1
+            cache.sched_advance(n)
+            if produced < max_new:
+                slot = chunks % 4
+                st.obs_host[slot, : 2 * B].copy_(cache.lens.view(-1), non_blocking=True)
+                if stops:
+                    st.obs_host[slot, 2 * B :].copy_(st.finished, non_blocking=True)
+                st.obs_ev[slot].record()
+                pending.append((slot, produced))
+        return produced

@@ -7,9 +7,9 @@ Everything else on the path is a hand-written HIP kernel behind the C ABI (inclu
 RMSNorm(+residual), RoPE+KV append, varlen prefill attention, ragged split-KV decode attention, SiLU*up,
 vision predictor, top-k select, token compaction, text predictor + eviction decision, greedy/advance.
 
-Round 6: this file is the API shell (construction, finalize(), forward(), generate() and their glue); the parameter tree and the vision side live in
-modules.py, the prompt layout / prefill planner / layer loop in prefill.py (PrefillEngine), the decode-step builders and their schedule in decode.py
-(DecodeScheduler) -- mixins of the one class the reference's harness sees.
+This file is the API shell (construction, finalize(), forward(), generate(), score()); the parameter tree and the vision side live in modules.py, the prompt layout /
+prefill planner / layer loop in prefill.py (PrefillEngine), the decode-step builders and their schedule in decode.py (DecodeScheduler) -- mixins of the one class the
+reference's harness sees.  generate() reads: parse + route (request.py), layout and prefill (prefill.py), arm and decode loop (decode.py), _score / _finish (here).
 
 Design (not a translation of the reference's op sequence):
   * activations are PACKED varlen [total_tokens, H] + cu_seqlens, never padded [B, N, H];
@@ -21,19 +21,16 @@ Design (not a translation of the reference's op sequence):
 """
 from __future__ import annotations
 
-import copy
-import math
+import dataclasses
 import operator
 import os
-from dataclasses import dataclass
-from typing import List, Optional, Tuple
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import logits_rules, logprobs, sampling, scoring
+from . import logprobs, request, sampling, scoring
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -469,7 +466,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 return self._forward_chunk(input_ids, attention_mask, cache)
             B = input_ids.shape[0]
             st = self._get_dstate(B, 0)
-            (cache.single_split_max_keys, cache.fused_single_keys), cache.min_keys_per_split = self._single_split_max_keys(st), self.min_keys_per_split
+            self._bind_schedule(st, cache)
             cache.ensure_capacity(2)
             self._rope_tables(max(cache.full_len_host) + 2)
             st.cur_ids.copy_(input_ids[:, 0])
@@ -492,11 +489,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                         cache.sched_observe(cache._sch["produced"], int(cache.lens[1].max()))
                         self.check_device_errors()  # the queue has just been drained anyway: a fused launch that gave up must not go unnoticed in a forward() loop either
                     cache.sched_chunk()
-            st.attn_ws.zero_()  # callers may interleave caches at equal positions on this state: clear the merge granules every call (see generate())
-            if st.qa_gran is not None:
-                st.qa_gran.zero_()
-            if st.tp_gran is not None:
-                st.tp_gran.zero_()
+            st.clear_granules()  # callers may interleave caches at equal positions on this state: every call
             self._decode_step_kernels(st, cache, False)
             use_tp = self._use_tp()
             cache.lens[0] += 1
@@ -531,35 +524,6 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
                 logits[b, : lens2[b]] = logits_packed[cu_list[b] : cu_list[b + 1]]
         return CausalLMOutputWithPast(logits=logits, past_key_values=cache)
 
-    def _gen_kwargs(self, kwargs, lens):
-        """Shared parsing of the HF generate() kwargs this path honours (DLL:117-152 forwards **kwargs to HF): rejects what is not
-        built instead of silently ignoring it."""
-        if "inputs_embeds" in kwargs:
-            raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
-        if (kwargs.get("num_beams", 1) or 1) != 1:
-            raise NotImplementedError("beam search is not built (harness default num_beams=1)")
-        max_new = kwargs.get("max_new_tokens")
-        if max_new is None:
-            max_new = 20 if kwargs.get("max_length") is None else int(kwargs["max_length"]) - max(lens)
-        if max_new < 1:
-            raise ValueError(f"max_new_tokens must be >= 1 (got {max_new})")
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
-        if isinstance(eos, (list, tuple)):
-            eos = [int(e) for e in eos]
-            eos = None if not eos else (eos[0] if len(eos) == 1 else eos)
-        elif eos is not None:
-            eos = int(eos)
-        pad = kwargs.get("pad_token_id", self.config.pad_token_id)
-        min_new = int(kwargs.get("min_new_tokens", 0) or 0)
-        return int(max_new), min(min_new, int(max_new)), eos, (0 if pad is None else int(pad))
-
-    def _logits_rules(self, kwargs):
-        """The request's logits processors (repetition_penalty, no_repeat_ngram_size, bad_words_ids), validated: logits_rules.Rules.  The EOS set is resolved as
-        _gen_kwargs resolves it (a one-token bad word equal to an EOS id is dropped, as in HF)."""
-        eos = kwargs.get("eos_token_id", self.config.eos_token_id)
-        eos_set = [] if eos is None else ([int(e) for e in eos] if isinstance(eos, (list, tuple)) else [int(eos)])
-        return logits_rules.normalize(kwargs, self.config.vocab_size, eos_set)
-
     @torch.no_grad()
     def _generate_sample(self, inputs, images, greedy=False, **kwargs):
         """`greedy=True` (round 4): the same plain loop over forward() taking the argmax -- the route for requests the device-side greedy loop does not
@@ -569,64 +533,27 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         Token streams cannot match HF's draw for draw (different RNG consumption); the distribution per step is the same.
         repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call.
         output_logprobs / top_logprobs: logprobs.reference_rows on every step's raw fp32 logits (the rule dl_decode_logprobs implements), masked behind a row's EOS."""
-        rules = self._logits_rules(kwargs)
-        n_lp = logprobs.validate(kwargs, self.config.vocab_size)
-        temperature = float(kwargs.get("temperature", 1.0) or 1.0)
-        top_k = int(kwargs.get("top_k", 0) or 0)
-        top_p = kwargs.get("top_p")
-        gen = kwargs.get("generator")
-        out = self.forward(inputs.to(self.device), attention_mask=kwargs.get("attention_mask"), images=images, image_features=kwargs.get("image_features"))
+        req = request.parse(kwargs, self.config)
+        out = self.forward(inputs.to(self.device), attention_mask=req.attention_mask, images=images, image_features=req.image_features)
         cache = out.past_key_values
-        max_new, min_new, eos, pad = self._gen_kwargs(kwargs, cache.full_len_host)
-        eos_set = [] if eos is None else (eos if isinstance(eos, list) else [eos])
-        # last VALID position of every row: the returned logits are right-padded with zeros when rows differ in length, and the
-        # last layer's KV length is the (compacted) row length
+        max_new = req.max_new(cache.full_len_host)
+        # last VALID position of every row: the logits are right-padded with zeros when rows differ in length; the last layer's KV length is the (compacted) row length
         last = cache[1][-1].to(self.device).long() - 1
-        logits = out.logits[torch.arange(out.logits.shape[0], device=self.device), last]
-        self.last_prefill_logits = logits.float().clone()
-        B = logits.shape[0]
-        finished = torch.zeros(B, dtype=torch.bool, device=self.device)
-        toks, scores, raw = [], [], []
-        for step in range(max_new):
-            z = logits.float()
-            if n_lp >= 0:
-                raw.append(z.clone())  # the model's own distribution: before the processors, the EOS ban and the warpers
-            if rules.on:
-                z = rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
-            z = z / temperature
-            if step < min_new and eos_set:
-                z[:, eos_set] = float("-inf")
-            if top_k > 0:
-                kth = torch.topk(z, min(top_k, z.shape[-1]), dim=-1).values[:, -1:]
-                z = z.masked_fill(z < kth, float("-inf"))
-            if top_p is not None and float(top_p) < 1.0:
-                sz, si = torch.sort(z, dim=-1, descending=False)
-                cum = sz.softmax(dim=-1).cumsum(dim=-1)
-                remove = cum <= (1.0 - float(top_p))
-                remove[:, -1] = False  # always keep the most probable token
-                z = z.masked_fill(remove.scatter(1, si, remove), float("-inf"))
-            scores.append(z)
-            nxt = z.argmax(dim=-1) if greedy else torch.multinomial(z.softmax(dim=-1), 1, generator=gen)[:, 0]
-            nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
-            toks.append(nxt)
-            for e in eos_set:
-                finished = finished | (nxt == e)
-            if eos_set and bool(finished.all()):
-                break
-            if step + 1 < max_new:
-                out = self.forward(nxt[:, None], past_key_values=cache)
-                cache = out.past_key_values
-                logits = out.logits[:, -1]
-        seq = torch.stack(toks, dim=1)
-        self.last_cache = cache
-        if kwargs.get("return_dict_in_generate"):
-            res = {"sequences": seq, "past_key_values": cache}
-            if kwargs.get("output_scores"):
-                res["scores"] = tuple(scores)
-            if n_lp >= 0:
-                res.update(logprobs.host_result(raw, seq, eos_set, n_lp))
-            return res
-        return seq
+        return self._host_decode(req, cache, out.logits[torch.arange(out.logits.shape[0], device=self.device), last].float(), max_new, greedy)
+
+    def _host_decode(self, req, cache, logits, max_new, greedy):
+        """A host route behind its first forward(): request.host_loop over single decode steps on `cache` -> the tokens [B, T_new], or generate()'s dict."""
+        self.last_prefill_logits = logits.clone()
+        toks, scores, raw = request.host_loop(logits, lambda nxt: self.forward(nxt[:, None], past_key_values=cache).logits[:, -1].float(), req, max_new, greedy)
+        seq, self.last_cache = torch.stack(toks, dim=1), cache
+        if not req.want_dict:
+            return seq
+        res = {"sequences": seq, "past_key_values": cache}
+        if req.want_scores:
+            res["scores"] = tuple(scores)
+        if req.n_lp >= 0:
+            res.update(logprobs.host_result(raw, seq, req.eos, req.n_lp))
+        return res
 
     @torch.no_grad()
     def _generate_on_cache(self, inputs, images, **kwargs):
@@ -637,9 +564,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         chunk-on-cache path (DML:2506-2521: the instruct predictor decides which of its K/V rows stay in layers >= sparse_layer), the new
         tokens through single decode steps; plain loop over forward(), no hipGraph.  repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process
         on every step's logits, on the tokens emitted in this call."""
-        rules = self._logits_rules(kwargs)
-        n_lp = logprobs.validate(kwargs, self.config.vocab_size)
-        if images is not None or kwargs.get("image_features") is not None:
+        req = request.parse(kwargs, self.config)
+        if images is not None or req.image_features is not None:
             raise NotImplementedError("generate(past_key_values=...) continues a dialogue: the image belongs to the first call")
         cache = kwargs["past_key_values"]
         if self.kv_cache_format is not None or getattr(cache, "kv_format", None) is not None:
@@ -657,42 +583,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             raise ValueError("generate(past_key_values=...) takes ONLY the new turn's token ids; these ids contain the image placeholder, i.e. the full dialogue "
                              "(the first turn, image included, is already in the cache)")
         # max_length counts what is already cached plus the new turn (the reference's own length accounting includes the 576 image tokens)
-        max_new, min_new, eos, pad = self._gen_kwargs({k: v for k, v in kwargs.items() if k != "past_key_values"}, [cache.seen_tokens + inputs.shape[1]])
-        eos_set = [] if eos is None else (eos if isinstance(eos, list) else [eos])
-        out = self.forward(inputs, attention_mask=kwargs.get("attention_mask"), past_key_values=cache)
-        cache = out.past_key_values
-        logits = out.logits[:, -1].float()
-        self.last_prefill_logits = logits.clone()
-        finished = torch.zeros(inputs.shape[0], dtype=torch.bool, device=self.device)
-        toks, scores, raw = [], [], []
-        for step in range(max_new):
-            if n_lp >= 0:
-                raw.append(logits.clone())  # the model's own distribution: before the processors and the EOS ban
-            z = rules.apply(logits, torch.stack(toks, dim=1) if toks else [[]] * inputs.shape[0]) if rules.on else logits.clone()
-            if step < min_new and eos_set:
-                z[:, eos_set] = float("-inf")
-            scores.append(z)
-            nxt = z.argmax(dim=-1)
-            nxt = torch.where(finished, torch.full_like(nxt, pad), nxt)
-            toks.append(nxt)
-            for e in eos_set:
-                finished = finished | (nxt == e)
-            if eos_set and bool(finished.all()):
-                break
-            if step + 1 < max_new:
-                out = self.forward(nxt[:, None], past_key_values=cache)
-                cache = out.past_key_values
-                logits = out.logits[:, -1].float()
-        seq = torch.stack(toks, dim=1)
-        self.last_cache = cache
-        if kwargs.get("return_dict_in_generate"):
-            res = {"sequences": seq, "past_key_values": cache}
-            if kwargs.get("output_scores"):
-                res["scores"] = tuple(scores)
-            if n_lp >= 0:
-                res.update(logprobs.host_result(raw, seq, eos_set, n_lp))
-            return res
-        return seq
+        max_new = req.max_new([cache.seen_tokens + inputs.shape[1]])
+        out = self.forward(inputs, attention_mask=req.attention_mask, past_key_values=cache)
+        req = dataclasses.replace(req, temperature=1.0, top_k=0, top_p=None)  # this route has never warped: the loop then is the plain argmax loop, bit for bit
+        return self._host_decode(req, out.past_key_values, out.logits[:, -1].float(), max_new, True)
 
     @torch.no_grad()
     def score(self, input_ids, labels, images=None, image_sizes=None, *, attention_mask=None, image_features=None, sync_every=None, output_logits=False):
@@ -750,294 +644,94 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
         the new token ids / pixels into static buffers."""
         self._check_ready()
-        rules = self._logits_rules(kwargs)  # validated here, before any launch
-        if rules.on and kwargs.get("_score_labels") is not None:
-            raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
-        n_lp = logprobs.validate(kwargs, self.config.vocab_size)  # -1: not asked for; else the number of alternatives per step
-        sampled = None  # (temperature, top_k, top_p, seed, row base) when the device sampler draws the tokens
-        if kwargs.get("do_sample", False):  # model_vqa_loader.py:162-175 passes do_sample = temperature > 0 (default 0: greedy)
-            if "inputs_embeds" in kwargs:
-                raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
-            if not sampling.device_route(kwargs, self.config.vocab_size, self.config.eos_token_id):  # (the EOS set resolved as _gen_kwargs resolves it)
-                return self._generate_sample(inputs, images, **kwargs)
-            # seed=<int>: the draw moves into the captured graphs (dl_decode_sample; the rule is sampling.py) and everything below is the greedy path's
-            # code.  The parameters are validated here, before any launch, and travel in device memory: no graph key knows them.
-            sampled = sampling.normalize_params(kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p")) + (int(kwargs["seed"]), int(kwargs.get("sample_row_base", 0) or 0))
-        if kwargs.get("past_key_values") is not None:
+        req = request.parse(kwargs, self.config, self.decode_sync_every)  # every keyword is validated here, before any launch
+        if req.route == "on_cache":
             return self._generate_on_cache(inputs, images, **kwargs)
-        if rules.on and not rules.device_route:
-            # past the device caps (logits_rules.MAX_*): the plain loop over forward(), which applies the same rule on the host -- sampled (torch's RNG) or greedy
-            if kwargs.get("do_sample", False):
-                return self._generate_sample(inputs, images, **kwargs)
+        if req.route == "host_sample":
+            return self._generate_sample(inputs, images, **kwargs)
+        if req.route == "host_greedy":
             return self._generate_sample(inputs, images, greedy=True, **{k: v for k, v in kwargs.items() if k not in ("do_sample", "sync_every")})
-        attention_mask = kwargs.get("attention_mask")
-        image_features = kwargs.get("image_features")
-        sync_every = int(kwargs.get("sync_every", self.decode_sync_every))  # decode steps enqueued between two observations of the device state
-        want_dict = bool(kwargs.get("return_dict_in_generate"))
-        want_logits = want_dict and bool(kwargs.get("output_logits"))  # HF: the raw (unprocessed) logits of every step
-        want_scores = want_dict and (bool(kwargs.get("output_scores")) or want_logits)
+        # ---- the device route: layout, cache / RoPE / state, arm, prefill (+ first token), decode loop, finish ----
         inputs = inputs.to(self.device)
-        tm = None
-        if self.record_timing:
-            tm = {"ev": [torch.cuda.Event(enable_timing=True) for _ in range(3)], "path": None}
+        tm = {"ev": [torch.cuda.Event(enable_timing=True) for _ in range(3)], "path": None} if self.record_timing else None
+        if tm is not None:
             tm["ev"][0].record()
-        n_feat = self._n_feat(images, image_features)
-        sc_ = self.config.sparse_config
-        vp_ = getattr(self.model, "image_score_predictor", None)
-        dev_layout = (self.device_prompt_layout and not kwargs.get("_host_layout") and attention_mask is None and n_feat > 0 and inputs.shape[1] >= 1
-                      and self.use_hip_graph and self.debug_records is None and not (sc_["use_text_predictor"] and sc_["use_instruct_predictor"])
-                      and not (vp_ is not None and (len(vp_._forward_hooks) or len(vp_._forward_pre_hooks)))
-                      and getattr(self.config, "tokenizer_model_max_length", None) is None)
-        if dev_layout:
-            # SURVEY 8f N1: ARCH:309-490 on the device.  Every row is assumed to hold exactly one image token (checked by the kernel; a
-            # violation is seen at the final synchronisation and the call is repeated with the host layout): all shapes then follow
-            # from (B, W), and where the image sits is the kernel's business, inside the captured graph.
-            # Round 4: W is rounded up to a WIDTH BUCKET -- the captured launches are sized for the bucket, the true width travels as a device
-            # scalar and the layout kernel packs the sequences at their true lengths (cu_seqlens, KV lengths, last rows: device memory the
-            # launches already read).  A request stream with a new width on every call (VQAL:123-196) then replays a handful of graphs.
-            Bq, Wq = inputs.shape
-            Wb = self._width_bucket(Wq, n_feat)
-            n_row, n_row_b = Wq - 1 + n_feat, Wb - 1 + n_feat
-            fake = [{"system": [0, 0], "image": [0, n_feat], "instruct": [n_feat, n_row_b], "answer": [n_row_b, n_row_b], "last_instruct": [n_feat, n_row_b]} for _ in range(Bq)]
-            lay = dict(sig=("dev", Bq, Wb, n_feat), B=Bq, lens=[n_row] * Bq, lens_bucket=[n_row_b] * Bq, indices=fake, text_src=[0], text_dst=[0], img_dst=[0], img_rows=list(range(Bq)),
-                       total=Bq * n_row_b, n_feat=n_feat, width=Wq, bucket=Wb)
-        else:
-            lay = self._layout(inputs, attention_mask, None, n_feat)
-        lens, indices, B = lay["lens"], lay["indices"], lay["B"]
-        max_new, min_new, eos, pad = self._gen_kwargs(kwargs, lens)
-        if isinstance(eos, list) and len(eos) > 3:
-            # three ids are compared on the device; a longer EOS set takes the plain forward() loop (same kernels per step, host-side stop test)
-            return self._generate_sample(inputs, images, greedy=True, **{k: v for k, v in kwargs.items() if k not in ("do_sample", "sync_every")})
+        lay, dev_layout = self._generate_layout(inputs, req, self._n_feat(images, req.image_features))
+        lens, B, max_new = lay["lens"], lay["B"], req.max_new(lay["lens"])
         cache = self._pooled_cache(B, max(lens) + max_new + 1)
         self._rope_tables(max(lens) + max_new + 1)
         st = self._get_dstate(B, max_new)
-        (cache.single_split_max_keys, cache.fused_single_keys), cache.min_keys_per_split = self._single_split_max_keys(st), self.min_keys_per_split
-        st.step.zero_(); st.finished.zero_(); st.decision.fill_(1)
-        # the in-kernel split merge of the decode attention validates its granules by tag = (position of the new token, layer): within one
-        # request positions only grow, so a slot left by an earlier step never matches -- but a slot left by an EARLIER REQUEST at the same
-        # position would.  Tag 0 is never expected: one clear per request makes every older granule unmatchable.
-        st.attn_ws.zero_()
-        if st.qa_gran is not None:
-            st.qa_gran.zero_()  # and of dl_gemv_qkv_attn
-        if st.tp_gran is not None:
-            st.tp_gran.zero_()  # and of dl_gemv_gu_tp
-        forced = kwargs.get("_score_labels")  # score(): int64 [B, T], validated there; the labels are device data like the sampling parameters -- one graph serves every sequence
-        # which bookkeeping kernel _first_token / the decode steps launch (and capture), and what it is told
-        self._mode = StepMode(eos=-1 if eos is None else (tuple(eos) if isinstance(eos, list) else eos), pad=pad, min_new=min_new, sampled=sampled is not None,
-                              forced=forced is not None, processed=rules.on, logprobs=n_lp)
-        if sampled is not None:
-            st.sample_params.copy_(ops.sample_params_words(*sampled))
-        if rules.on:  # the settings are device data like the sampling parameters: one graph serves every penalty, n-gram size and word list
-            st.logits_params.copy_(ops.logits_params_words(rules.repetition_penalty, rules.no_repeat_ngram_size, len(rules.bad_words)))
-            st.bad_words.copy_(ops.bad_words_table(rules.bad_words, "cpu"))
-        if forced is not None:
-            st.labels.fill_(scoring.IGNORE)
-            st.labels[:, : forced.shape[1]].copy_(forced)
-            st.nll.zero_()
-            st.top1.fill_(-1)
-        if n_lp >= 0:  # dl_decode_logprobs' outputs: slots of this request that no launch reaches must not show an earlier request's values
-            st.need_logprobs()
-            st.lp.zero_(); st.top_lp.zero_(); st.top_ids.fill_(-1)
-        if getattr(self, "_prefill_logits_buf", None) is None or self._prefill_logits_buf.shape != st.logits.shape:
-            self._prefill_logits_buf = torch.empty(st.logits.shape, dtype=torch.float32, device=self.device)
-        vp = getattr(self.model, "image_score_predictor", None)
-        hooked = vp is not None and (len(vp._forward_hooks) or len(vp._forward_pre_hooks))
-        graphable = self.use_hip_graph and self.debug_records is None and not hooked  # (the instruct predictor's data-dependent row count stays on the device)
-        prefill_path = "eager"
-        if graphable:
-            # ADVICE r3: the instruct predictor's compaction span is baked into the captured plan, and `sig` ignores token values: two
-            # equally long multi-turn prompts whose last "USER:" sits elsewhere must not share a graph
-            li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
-            key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
-                   cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._mode, repr(self.config.sparse_config), li_key,
-                   self._prefill_knob_key(), self._kv_format_key(cache))  # (ADVICE r5: a knob toggled at run time must not replay a graph captured under the other setting)
-            ent = self._prefill_graphs.get(key)
-            if ent is None:
-                # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
-                # such as the VQA loader's, VQAL:123-196, presents many widths; capturing each on sight cost two prefills + a capture per miss)
-                self._evict_prefill_entries()
-                ids0 = inputs.contiguous().clone()
-                if dev_layout and lay["bucket"] != lay["width"]:
-                    ids0 = torch.zeros((B, lay["bucket"]), dtype=inputs.dtype, device=self.device)
-                ent = dict(ids=ids0, images=None if images is None else images.to(self.device).clone(),
-                           feats=None if image_features is None else image_features.to(self.device).clone(),
-                           plan=self._plan_prefill(lay.get("lens_bucket", lens), indices), indices=copy.deepcopy(indices), graph=None)
-                ent["plan"]["device_instruct"] = True
-                if dev_layout:
-                    ent["w_true"] = torch.zeros(1, dtype=torch.int32, device=self.device)
-                    ent["didx"] = ops.prompt_layout(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS)  # allocates the outputs (its launch saw an empty bucket buffer:
-                    ent["didx"]["err"].zero_()                                                        # forget that verdict)
-                    ent["plan"]["img_start"] = ent["didx"]["img_start"]  # written by the layout kernel inside the graph
-                else:
-                    ent["didx"] = self._dev_idx(lay)
-
-                def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st):
-                    if dev_layout:
-                        p_ = ent["plan"]  # the plan's shapes are the bucket's; its device metadata is (re)written here at the true width
-                        ops.prompt_layout_into(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS, ent["didx"], w_true=ent["w_true"], n_drop=(p_["n_img"] - p_["k"]) if p_["vision_on"] else 0,
-                                               cu=p_["cu"], cu2=p_["cu2"], lens=p_["lens_dev"], last_rows=p_["last_rows"])
-                    f = ent["feats"] if ent["feats"] is not None else (self.encode_images(ent["images"]) if ent["images"] is not None else None)
-                    emb = self._assemble(lay, ent["didx"], ent["ids"], f)
-                    x = self._prefill_run(ent["plan"], emb, cache, copy.deepcopy(ent["indices"]), True)
-                    self._first_token(st, x)
-
-                ent["run"] = run
-                self._prefill_graphs[key] = ent
-                if dev_layout:
-                    ent["ids"][:, : inputs.shape[1]].copy_(inputs)
-                    ent["w_true"].fill_(inputs.shape[1])
-                st.step.zero_(); st.finished.zero_()
-                run()
-            else:
-                self._prefill_graphs[key] = self._prefill_graphs.pop(key)  # most recently used last
-                ent["ids"][:, : inputs.shape[1]].copy_(inputs)
-                if dev_layout:
-                    ent["w_true"].fill_(inputs.shape[1])
-                if images is not None:
-                    ent["images"].copy_(images)
-                if image_features is not None:
-                    ent["feats"].copy_(image_features)
-                if ent["graph"] is None:
-                    # second sighting: capture (the eager run of the first sighting was the warm-up: library heuristics, allocator); all
-                    # prefill graphs record into ONE memory pool -- they never run concurrently and leave nothing behind in it (logits, ids
-                    # and K/V land in persistent buffers), so a hundred cached shapes cost one shape's activations
-                    prefill_path = "graph-capture"
-                    if self._prefill_pool is None or not any(e["graph"] is not None for e in self._prefill_graphs.values()):
-                        # (the allocator drops a private pool with its last graph: a handle whose graphs are all gone must not be reused)
-                        self._prefill_pool = torch.cuda.graph_pool_handle()
-                    g_ = torch.cuda.CUDAGraph()
-                    with no_gc_during_capture(), torch.cuda.graph(g_, pool=self._prefill_pool):
-                        ent["run"]()
-                    ent["graph"] = g_
-                    ent["run"] = None
-                else:
-                    prefill_path = "graph-replay"
-                st.step.zero_(); st.finished.zero_()
-                ent["graph"].replay()
-            p_host = ent["plan"]
-            if dev_layout and lay["bucket"] != lay["width"]:  # host mirrors follow the true lengths, not the bucket's
-                drop_ = (p_host["n_img"] - p_host["k"]) if p_host["vision_on"] else 0
-                p_host = dict(p_host, lens=list(lens), lens2=[n - drop_ for n in lens] if self.config.sparse_config["sparse_layer"] < self.config.num_hidden_layers else list(lens))
-            self._prefill_host_update(p_host, cache, indices)
-        else:
-            f = image_features if image_features is not None else (self.encode_images(images) if images is not None else None)
-            embeds = self._assemble(lay, self._dev_idx(lay), inputs, f)
-            x, cache, _, _ = self._prefill(embeds, lens, indices, cache, reserve=max_new + 1, last_only=True)
-            self._first_token(st, x)
+        self._bind_schedule(st, cache)
+        self._arm(st, req, max_new)
+        ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new)
         self.last_prefill_logits = self._prefill_logits_buf
         if tm is not None:
             tm["ev"][1].record()
             tm["path"] = prefill_path
         scores, raw_logits = [], []
-
-        eos_ids = [] if self._mode.eos == -1 else (list(self._mode.eos) if isinstance(self._mode.eos, tuple) else [self._mode.eos])
-
-        def _score(step_idx):  # HF `scores`: the processed logits of that step (EOS at -inf while step < min_new_tokens)
-            z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
-            if want_logits:
-                raw_logits.append(z.clone())
-            if self._mode.processed:  # what dl_logits_process left for this step's bookkeeping launch (the buffer is read after every step on this route)
-                z = st.proc_logits.clone()
-            if sampled is not None:  # the processed logits of a sampled step: z = logit / T with -inf outside the kept set (sampling.py), as HF reports them
-                # (on the host side of the loop, with the contract's own arithmetic: this branch reads the step buffer after every step anyway)
-                scores.append(sampling.processed_logits(z.cpu(), sampled[0], sampled[1], sampled[2], eos_ids if step_idx < min_new else ()).to(z.device))
-                return
-            if step_idx < min_new and eos_ids:
-                z[:, eos_ids] = float("-inf")
-            scores.append(z)
-
-        if want_scores:
-            _score(0)
-        # ---- decode loop: chunks of captured steps, scheduled from the lengths the predictor actually leaves (DML:2377-2391, CU:153-164) ----
-        # Before a chunk the host knows: the un-evicted group's length exactly, and the evicted group's as OBSERVED after an earlier chunk
-        # (non-blocking copy into pinned memory, consumed one chunk late so that the host never waits for steps it has just enqueued) plus
-        # the steps enqueued since.  Those bounds pick the split-KV factor / the fused q|k|v+attention launch (cache.n_splits), i.e. which
-        # captured graph is replayed; the values are data, never timing, so the schedule is deterministic for a given request.
-        produced, chunks = 1, 0
-        cache.sched_begin(max(cache.full_len_host), getattr(cache, "prefill_sparse_max", None) or max(cache.full_len_host), sync_every)
-        pending = []  # (ring slot, produced-when-copied)
-        all_done = False
-        while produced < max_new and not all_done:
-            # EOS of a short answer (VQA: a few tokens) must not cost two chunks of wasted steps: the first chunks' flags are read blocking (one
-            # ~50 us queue drain each), later ones one chunk late.  The SCHEDULE never uses an observation newer than one chunk old either way.
-            keep_newest = 0 if (eos_ids and chunks <= 2) else 1
-            while len(pending) > keep_newest:
-                slot, at = pending.pop(0)
-                st.obs_ev[slot].synchronize()
-                row = st.obs_host[slot]
-                cache.sched_observe(at, int(row[B : 2 * B].max()))
-                if (eos_ids or self._mode.forced) and int(row[2 * B :].min()) != 0:  # (score(): finished = labels exhausted)
-                    all_done = True
-            if all_done:
-                break
-            n = min(cache.sched_chunk(), max_new - produced)
-            if want_scores:  # the step buffer is read after every step; the schedule (chunks, bounds) is the same as without scores
-                for i_ in range(n):
-                    self._run_decode_steps(st, cache, 1)
-                    _score(produced + i_)
-            else:
-                self._run_decode_steps(st, cache, n)
-            produced += n
-            chunks += 1
-            cache.sched_advance(n)
-            if produced < max_new:
-                slot = chunks % 4
-                st.obs_host[slot, : 2 * B].copy_(cache.lens.view(-1), non_blocking=True)
-                if eos_ids or self._mode.forced:
-                    st.obs_host[slot, 2 * B :].copy_(st.finished, non_blocking=True)
-                st.obs_ev[slot].record()
-                pending.append((slot, produced))
+        on_step = (lambda j: self._score(req, st, j, scores, raw_logits)) if (req.want_scores or req.want_logits) else None
+        if on_step is not None:
+            on_step(0)
+        produced = self._decode_loop(st, cache, max_new, req.sync_every, on_step)
         if B == 1 or self._lp_ws is not None:
-            # (ADVICE r5: batched decode and the packed prefill also contain in-kernel hand-overs -- dl_linear_packed with k ranges, reporting through
-            # _lp_err -- so a reducer timeout must be seen for B > 1 too; generate() is about to synchronise for its result anyway)
-            self.check_device_errors()
+            self.check_device_errors()  # (B > 1 too: dl_linear_packed's k ranges hand over in-kernel, through _lp_err; generate() is about to synchronise for its result anyway)
         if dev_layout and int(ent["didx"]["err"].item()) != 0:
             # a row without exactly one image token (text-only row, several images): what was computed is meaningless -- repeat the
             # call with the host-side layout, which handles (or rejects) those rows like the reference does
             ent["didx"]["err"].zero_()
             return self.generate(inputs, images=images, image_sizes=image_sizes, _host_layout=True, **kwargs)
-        # host mirrors of what the device loop advanced: every row's un-evicted length grows by one per decode step
-        cache.full_len_host = [n + produced - 1 for n in cache.full_len_host]
+        return self._finish(req, st, cache, produced, scores, raw_logits, tm)
+
+    def _score(self, req, st, step_idx, scores, raw_logits):
+        """The device route's per-step callback: appends HF's `scores` of the step (the processed logits, EOS at -inf while step < min_new_tokens) and the raw logits."""
+        z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
+        if req.want_logits:
+            raw_logits.append(z.clone())
+        if req.rules.on:  # what dl_logits_process left for this step's bookkeeping launch
+            z = st.proc_logits.clone()
+        banned = list(req.eos) if step_idx < req.min_new else []
+        if req.sampled is not None:  # z = logit / T with -inf outside the kept set, as HF reports a sampled step: on the host, with the contract's own arithmetic (sampling.py)
+            z = sampling.processed_logits(z.cpu(), *req.sampled[:3], banned).to(z.device)
+        elif banned:
+            z[:, banned] = float("-inf")
+        scores.append(z)
+
+    def _finish(self, req, st, cache, produced, scores, raw_logits, tm):
+        """The device route's result: the host mirrors of what the loop advanced, the EOS trim, then the tokens, generate()'s dict or score()'s."""
+        cache.full_len_host = [n + produced - 1 for n in cache.full_len_host]  # every row's un-evicted length grows by one per decode step
         cache.seen_tokens += produced - 1
         out = st.out_ids[:, :produced].clone()
-        if eos_ids:  # HF stops as soon as every row has emitted EOS: trim the columns produced after that
-            hit = out == eos_ids[0]
-            for e_ in eos_ids[1:]:
+        if req.eos:  # HF stops as soon as every row has emitted EOS: trim the columns produced after that
+            hit = out == req.eos[0]
+            for e_ in req.eos[1:]:
                 hit = hit | (out == e_)
-            fin = hit.int().cumsum(dim=1).clamp(max=1)
-            all_done = fin.min(dim=0).values
+            all_done = hit.int().cumsum(dim=1).clamp(max=1).min(dim=0).values
             if bool(all_done.any().item()):
                 first = int(torch.argmax(all_done).item())
-                out = out[:, : first + 1]
-                scores = scores[: first + 1]
-                raw_logits = raw_logits[: first + 1]
+                out, scores, raw_logits = out[:, : first + 1], scores[: first + 1], raw_logits[: first + 1]
         self.last_cache = cache
         if tm is not None:
             tm["ev"][2].record()
             tm["new_tokens"] = int(out.shape[1])
             self.last_timing = tm
-        if forced is not None:
-            # score(): the caller gets an independent COPY of the cache -- a perplexity run is many calls of one shape, and detaching the pooled slab (as below)
-            # would drop the captured graphs after every one of them
-            return {"sequences": out, "past_key_values": cache.detached_copy(), "logits": tuple(raw_logits), "nll": st.nll[:, : forced.shape[1]].clone(),
-                    "top1": st.top1[:, : forced.shape[1]].clone()}
-        if want_dict:
-            # the caller keeps this cache (the reference returns an independent one per call): detach it from the pool, the next
-            # generate() allocates a fresh slab instead of overwriting this one
-            self._cache_pool = None
-            ptr = cache.slab.data_ptr()  # captured graphs hold raw pointers into the slab the caller now owns (and may free): drop them
-            self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if ptr not in k}
-            st.graphs = {k: v for k, v in st.graphs.items() if ptr not in k}
-            res = {"sequences": out, "past_key_values": cache}
-            if want_scores and kwargs.get("output_scores"):
-                res["scores"] = tuple(scores)
-            if want_logits:
-                res["logits"] = tuple(raw_logits)
-            if n_lp >= 0:  # the columns `sequences` kept; after a row's first EOS (pad in `sequences`) 0.0 / -1
-                W = out.shape[1]
-                lp, top_lp, top_ids = logprobs.mask_after_eos(out, eos_ids, st.lp[:, :W].clone(), st.top_lp[:, :W, :n_lp].clone(), st.top_ids[:, :W, :n_lp].clone())
-                res["logprobs"] = lp
-                if n_lp > 0:
-                    res["top_logprobs"], res["top_logprob_ids"] = top_lp, top_ids
-            return res
-        return out
+        if req.forced is not None:
+            T = req.forced.shape[1]  # (the cache: an independent COPY -- a perplexity run is many calls of one shape, and detaching the slab, as below, would drop the graphs after each)
+            return {"sequences": out, "past_key_values": cache.detached_copy(), "logits": tuple(raw_logits), "nll": st.nll[:, :T].clone(), "top1": st.top1[:, :T].clone()}
+        if not req.want_dict:
+            return out
+        # the caller keeps this cache (the reference returns an independent one per call): detach it from the pool, the next generate() allocates a fresh
+        # slab instead of overwriting this one; captured graphs hold raw pointers into the slab the caller now owns (and may free): drop them
+        self._cache_pool = None
+        self._drop_graphs_on(cache.slab.data_ptr())
+        res = {"sequences": out, "past_key_values": cache}
+        if req.want_scores:
+            res["scores"] = tuple(scores)
+        if req.want_logits:
+            res["logits"] = tuple(raw_logits)
+        if req.n_lp >= 0:  # the columns `sequences` kept; after a row's first EOS (pad in `sequences`) 0.0 / -1
+            W, n = out.shape[1], req.n_lp
+            lp, top_lp, top_ids = logprobs.mask_after_eos(out, req.eos, st.lp[:, :W].clone(), st.top_lp[:, :W, :n].clone(), st.top_ids[:, :W, :n].clone())
+            res["logprobs"] = lp
+            if n > 0:
+                res["top_logprobs"], res["top_logprob_ids"] = top_lp, top_ids
+        return res

@@ -1,20 +1,17 @@
-"""Prefill side of the engine: prompt layout (ARCH:169-601 on the host and on the device), the prefill planner, the packed-varlen layer loop with the sparsification at layer `sparse_layer` (DML:1656-2594), the prefill-shape graph cache, chunk-on-cache and no-KV-cache forwards.  A mixin of DynamicLlavaLlamaForCausalLM (model.py); split out in round 6 (no behaviour change)."""
+"""Prefill side of the engine: prompt layout (ARCH:169-601 on the host and on the device), the prefill planner, the packed-varlen layer loop with the sparsification at layer `sparse_layer` (DML:1656-2594), the prefill-shape graph cache, chunk-on-cache and no-KV-cache forwards; of generate()'s stages, the layout decision (_generate_layout) and the prefill with its eager-first / capture-second / replay-after graph cache (_generate_prefill).  A mixin of DynamicLlavaLlamaForCausalLM (model.py)."""
 from __future__ import annotations
 
-
 import copy
-import math
 import os
-from dataclasses import dataclass
-from typing import List, Optional, Tuple
+from typing import List, Optional
 
 import torch
-import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
 from .cache import KVSlabCache
-from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
+from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX
+from .decode import no_gc_during_capture
 from .modules import CausalLMOutputWithPast
 
 USER_IDS = [11889, 29901]  # "USER:" -- llava/model/dynamic_llava_arch.py:36
@@ -553,6 +550,110 @@ class PrefillEngine:
         seen = [k for k, e in self._prefill_graphs.items() if e["graph"] is None]
         for k in graphs[: max(0, len(graphs) - cap + 1)] + seen[: max(0, len(seen) - cap + 1)]:
             self._prefill_graphs.pop(k)
+
+    def _generate_layout(self, inputs, req, n_feat):
+        """generate()'s prompt layout -> (lay, dev_layout): a device kernel inside the captured prefill lays the prompt out and `lay` only names shapes, or _layout's."""
+        sc, vp = self.config.sparse_config, getattr(self.model, "image_score_predictor", None)
+        dev_layout = (self.device_prompt_layout and not req.host_layout and req.attention_mask is None and n_feat > 0 and inputs.shape[1] >= 1
+                      and self.use_hip_graph and self.debug_records is None and not (sc["use_text_predictor"] and sc["use_instruct_predictor"])
+                      and not (vp is not None and (len(vp._forward_hooks) or len(vp._forward_pre_hooks)))
+                      and getattr(self.config, "tokenizer_model_max_length", None) is None)
+        if not dev_layout:
+            return self._layout(inputs, req.attention_mask, None, n_feat), False
+        # SURVEY 8f N1: ARCH:309-490 on the device.  Every row is assumed to hold exactly one image token (checked by the kernel; a violation is seen at the final
+        # synchronisation and the call is repeated with the host layout): all shapes then follow from (B, W).  W is rounded up to a WIDTH BUCKET -- the captured
+        # launches are sized for the bucket, the true width travels as a device scalar and the layout kernel packs the sequences at their true lengths (cu_seqlens,
+        # KV lengths, last rows) -- so a request stream with a new width on every call (VQAL:123-196) replays a handful of graphs.
+        Bq, Wq = inputs.shape
+        Wb = self._width_bucket(Wq, n_feat)
+        n_row, n_row_b = Wq - 1 + n_feat, Wb - 1 + n_feat
+        fake = [{"system": [0, 0], "image": [0, n_feat], "instruct": [n_feat, n_row_b], "answer": [n_row_b, n_row_b], "last_instruct": [n_feat, n_row_b]} for _ in range(Bq)]
+        return dict(sig=("dev", Bq, Wb, n_feat), B=Bq, lens=[n_row] * Bq, lens_bucket=[n_row_b] * Bq, indices=fake, text_src=[0], text_dst=[0], img_dst=[0], img_rows=list(range(Bq)),
+                    total=Bq * n_row_b, n_feat=n_feat, width=Wq, bucket=Wb), True
+
+    def _generate_prefill(self, lay, dev_layout, inputs, images, image_features, cache, st, max_new):
+        """generate()'s prefill, the first token's bookkeeping launch included -> (entry of _prefill_graphs, path: "eager" on a shape's first sighting, then
+        "graph-capture", then "graph-replay"); a model that cannot be captured (use_hip_graph off, debug_records, hooks) keeps no entry: (None, "eager")."""
+        lens, indices, B, n_feat = lay["lens"], lay["indices"], lay["B"], lay["n_feat"] if dev_layout else None
+        vp = getattr(self.model, "image_score_predictor", None)
+        if not (self.use_hip_graph and self.debug_records is None) or (vp is not None and (len(vp._forward_hooks) or len(vp._forward_pre_hooks))):  # not capturable
+            f = image_features if image_features is not None else (self.encode_images(images) if images is not None else None)
+            embeds = self._assemble(lay, self._dev_idx(lay), inputs, f)
+            x, _, _, _ = self._prefill(embeds, lens, indices, cache, reserve=max_new + 1, last_only=True)
+            self._first_token(st, x)
+            return None, "eager"
+        # ADVICE r3: the instruct predictor's compaction span is baked into the captured plan, and `sig` ignores token values: two
+        # equally long multi-turn prompts whose last "USER:" sits elsewhere must not share a graph
+        li_key = tuple(tuple(ix["last_instruct"]) for ix in indices) if self._instruct_on(indices, B) else None
+        key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
+               cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._mode, repr(self.config.sparse_config), li_key,
+               self._prefill_knob_key(), self._kv_format_key(cache))  # (ADVICE r5: a knob toggled at run time must not replay a graph captured under the other setting)
+        ent = self._prefill_graphs.get(key)
+        path = "eager" if ent is None else ("graph-capture" if ent["graph"] is None else "graph-replay")
+        if ent is None:
+            # first sighting of a prompt shape: run it eagerly ONCE, through the same closure a capture would record (a request stream
+            # such as the VQA loader's, VQAL:123-196, presents many widths; capturing each on sight cost two prefills + a capture per miss)
+            self._evict_prefill_entries()
+            ids0 = inputs.contiguous().clone()
+            if dev_layout and lay["bucket"] != lay["width"]:
+                ids0 = torch.zeros((B, lay["bucket"]), dtype=inputs.dtype, device=self.device)
+            ent = dict(ids=ids0, images=None if images is None else images.to(self.device).clone(),
+                       feats=None if image_features is None else image_features.to(self.device).clone(),
+                       plan=self._plan_prefill(lay.get("lens_bucket", lens), indices), indices=copy.deepcopy(indices), graph=None)
+            ent["plan"]["device_instruct"] = True
+            if dev_layout:
+                ent["w_true"] = torch.zeros(1, dtype=torch.int32, device=self.device)
+                ent["didx"] = ops.prompt_layout(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS)  # allocates the outputs (its launch saw an empty bucket buffer:
+                ent["didx"]["err"].zero_()                                                        # forget that verdict)
+                ent["plan"]["img_start"] = ent["didx"]["img_start"]  # written by the layout kernel inside the graph
+            else:
+                ent["didx"] = self._dev_idx(lay)
+
+            def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st):
+                if dev_layout:
+                    p_ = ent["plan"]  # the plan's shapes are the bucket's; its device metadata is (re)written here at the true width
+                    ops.prompt_layout_into(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS, ent["didx"], w_true=ent["w_true"], n_drop=(p_["n_img"] - p_["k"]) if p_["vision_on"] else 0,
+                                           cu=p_["cu"], cu2=p_["cu2"], lens=p_["lens_dev"], last_rows=p_["last_rows"])
+                f = ent["feats"] if ent["feats"] is not None else (self.encode_images(ent["images"]) if ent["images"] is not None else None)
+                emb = self._assemble(lay, ent["didx"], ent["ids"], f)
+                x = self._prefill_run(ent["plan"], emb, cache, copy.deepcopy(ent["indices"]), True)
+                self._first_token(st, x)
+
+            ent["run"] = run
+            self._prefill_graphs[key] = ent
+            if dev_layout:
+                ent["ids"][:, : inputs.shape[1]].copy_(inputs)
+                ent["w_true"].fill_(inputs.shape[1])
+            st.step.zero_(); st.finished.zero_()
+            run()
+        else:
+            self._prefill_graphs[key] = self._prefill_graphs.pop(key)  # most recently used last
+            ent["ids"][:, : inputs.shape[1]].copy_(inputs)
+            if dev_layout:
+                ent["w_true"].fill_(inputs.shape[1])
+            if images is not None:
+                ent["images"].copy_(images)
+            if image_features is not None:
+                ent["feats"].copy_(image_features)
+            if ent["graph"] is None:
+                # second sighting: capture (the eager run of the first sighting was the warm-up: library heuristics, allocator); all prefill graphs record into ONE memory
+                # pool -- they never run concurrently and leave nothing behind in it (logits, ids, K/V land in persistent buffers): a hundred shapes cost one shape's activations
+                if self._prefill_pool is None or not any(e["graph"] is not None for e in self._prefill_graphs.values()):
+                    # (the allocator drops a private pool with its last graph: a handle whose graphs are all gone must not be reused)
+                    self._prefill_pool = torch.cuda.graph_pool_handle()
+                g_ = torch.cuda.CUDAGraph()
+                with no_gc_during_capture(), torch.cuda.graph(g_, pool=self._prefill_pool):
+                    ent["run"]()
+                ent["graph"] = g_
+                ent["run"] = None
+            st.step.zero_(); st.finished.zero_()
+            ent["graph"].replay()
+        p_host = ent["plan"]
+        if dev_layout and lay["bucket"] != lay["width"]:  # host mirrors follow the true lengths, not the bucket's
+            drop_ = (p_host["n_img"] - p_host["k"]) if p_host["vision_on"] else 0
+            p_host = dict(p_host, lens=list(lens), lens2=[n - drop_ for n in lens] if self.config.sparse_config["sparse_layer"] < self.config.num_hidden_layers else list(lens))
+        self._prefill_host_update(p_host, cache, indices)
+        return ent, path
 
     def _unpad_embeds(self, inputs_embeds, attention_mask, input_embeds_indices):
         """Padded [B, N, H] embeddings (what prepare_inputs_labels_for_multimodal returns: right- OR left-padded, ARCH:529-579) ->

@@ -1,0 +1,123 @@
+"""A generate() request, parsed by one function: the keywords resolved and validated before any device work (Request), the route it takes (route), and the one host loop both
+host routes run (host_loop).  Pure Python on torch tensors.  (The host routes keep their **kwargs signatures: a request generate() hands to one is parsed there a second time.)"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Any, Optional, Tuple
+
+import torch
+
+from . import logits_rules, logprobs, sampling
+from .sampling import eos_ids  # the only resolver of eos_token_id; defined in that leaf module because sampling.device_route needs it too
+
+
+def route(kwargs, rules, vocab_size, default_eos) -> str:
+    """Which body of generate() serves the kwargs (the table is in DESIGN.md): "device" (the captured graphs), "host_sample" (_generate_sample), "host_greedy"
+    (_generate_sample(greedy=True), without do_sample / sync_every) or "on_cache" (_generate_on_cache).  Past the device caps -- logits_rules.MAX_*, or more EOS
+    ids than the step-closing kernels compare -- a request takes the plain loop over forward(), which applies the same rule on the host."""
+    sample = bool(kwargs.get("do_sample", False))
+    if sample and not sampling.device_route(kwargs, vocab_size, default_eos):
+        return "host_sample"  # (KNOWN DEFECT: with past_key_values too -- _generate_sample never reads them, the dialogue is dropped without a word)
+    if kwargs.get("past_key_values") is not None:
+        return "on_cache"
+    if (rules.on and not rules.device_route) or len(eos_ids(kwargs, default_eos)) > sampling.MAX_EOS_IDS:
+        return "host_sample" if sample else "host_greedy"
+    return "device"
+
+
+@dataclass(frozen=True)
+class Request:
+    """Everything generate() and its host routes read from **kwargs."""
+    eos: Tuple[int, ...]
+    pad: int
+    min_new: int  # as asked for; capped at max_new where it is used
+    rules: logits_rules.Rules
+    n_lp: int  # -1: no log-probabilities; else the number of alternatives per step
+    sampled: Optional[tuple]  # (temperature, top_k, top_p, seed, row base) when the device sampler draws the tokens
+    temperature: float  # the host loop's warpers (torch's RNG)
+    top_k: int
+    top_p: Optional[float]
+    generator: Any
+    want_dict: bool
+    want_scores: bool  # `scores` in the result: the processed logits of every step
+    want_logits: bool  # `logits` in the result: the raw ones (either makes the device loop read the step buffer after every step)
+    sync_every: Optional[int]  # None: the model's decode_sync_every
+    forced: Any  # score(): int64 [B, T] labels, validated there
+    attention_mask: Any
+    image_features: Any
+    host_layout: bool
+    route: str
+    max_new_tokens: Optional[int]
+    max_length: Optional[int]
+
+    def max_new(self, lens) -> int:
+        """The number of steps: max_new_tokens, or max_length - the longest prompt (HF's default: 20 steps)."""
+        n = self.max_new_tokens
+        if n is None:
+            n = 20 if self.max_length is None else int(self.max_length) - max(lens)
+        if n < 1:
+            raise ValueError(f"max_new_tokens must be >= 1 (got {n})")
+        return int(n)
+
+
+def parse(kwargs, config, sync_every=None) -> Request:
+    """generate()'s **kwargs -> Request.  Every keyword is validated here, before any device work, in this order: the logits processors, score() with
+    processors, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), the sampling parameters."""
+    V, eos = config.vocab_size, eos_ids(kwargs, config.eos_token_id)
+    rules = logits_rules.normalize(kwargs, V, eos)  # (a one-token bad word equal to an EOS id is dropped, as in HF)
+    forced = kwargs.get("_score_labels")
+    if rules.on and forced is not None:
+        raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
+    n_lp = logprobs.validate(kwargs, V)
+    if "inputs_embeds" in kwargs:
+        raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
+    if (kwargs.get("num_beams", 1) or 1) != 1:
+        raise NotImplementedError("beam search is not built (harness default num_beams=1)")
+    rt, sampled = route(kwargs, rules, V, config.eos_token_id), None
+    if kwargs.get("do_sample", False) and sampling.device_route(kwargs, V, config.eos_token_id):
+        # seed=<int>: the draw moves into the captured graphs (device data, in no graph key).  Validated whatever the route: processors past the device caps still send it to the host loop
+        sampled = sampling.normalize_params(kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p")) + (int(kwargs["seed"]), int(kwargs.get("sample_row_base", 0) or 0))
+    want_dict, pad, top_p = bool(kwargs.get("return_dict_in_generate")), kwargs.get("pad_token_id", config.pad_token_id), kwargs.get("top_p")
+    return Request(eos=eos, pad=0 if pad is None else int(pad), min_new=int(kwargs.get("min_new_tokens", 0) or 0), rules=rules, n_lp=n_lp, sampled=sampled if rt == "device" else None,
+                   temperature=float(kwargs.get("temperature", 1.0) or 1.0), top_k=int(kwargs.get("top_k", 0) or 0), top_p=None if top_p is None else float(top_p),
+                   generator=kwargs.get("generator"), want_dict=want_dict, want_scores=want_dict and bool(kwargs.get("output_scores")), want_logits=want_dict and bool(kwargs.get("output_logits")),
+                   sync_every=sync_every if kwargs.get("sync_every") is None else int(kwargs["sync_every"]), forced=forced, attention_mask=kwargs.get("attention_mask"),
+                   image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"))
+
+
+def host_loop(logits, advance, req: Request, max_new: int, greedy: bool):
+    """The plain decoding loop of the host routes.  logits: the first step's fp32 [B, V]; advance(next_ids [B]) -> the next step's, called once per token but the
+    last.  Per step, in HF's order: the logits processors on the tokens emitted in this call, temperature, the EOS ban of min_new_tokens, top-k, top-p, then the
+    argmax (`greedy`) or a draw with torch's generator; pad behind a row's EOS; stops when every row has finished.  -> (tokens: a list of [B], scores: the
+    processed logits per step, raw: the model's own logits per step, kept only when log-probabilities are asked for).  No device work of its own."""
+    B, eos = logits.shape[0], list(req.eos)
+    finished = torch.zeros(B, dtype=torch.bool, device=logits.device)
+    toks, scores, raw = [], [], []
+    for step in range(max_new):
+        z = logits
+        if req.n_lp >= 0:
+            raw.append(z.clone())
+        if req.rules.on:
+            z = req.rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
+        z = z / req.temperature  # (a new tensor; / 1.0 is exact)
+        if step < req.min_new and eos:
+            z[:, eos] = float("-inf")
+        if req.top_k > 0:
+            kth = torch.topk(z, min(req.top_k, z.shape[-1]), dim=-1).values[:, -1:]
+            z = z.masked_fill(z < kth, float("-inf"))
+        if req.top_p is not None and req.top_p < 1.0:
+            sz, si = torch.sort(z, dim=-1, descending=False)
+            remove = sz.softmax(dim=-1).cumsum(dim=-1) <= (1.0 - req.top_p)
+            remove[:, -1] = False  # always keep the most probable token
+            z = z.masked_fill(remove.scatter(1, si, remove), float("-inf"))
+        scores.append(z)
+        nxt = z.argmax(dim=-1) if greedy else torch.multinomial(z.softmax(dim=-1), 1, generator=req.generator)[:, 0]
+        nxt = torch.where(finished, torch.full_like(nxt, req.pad), nxt)
+        toks.append(nxt)
+        for e in eos:
+            finished = finished | (nxt == e)
+        if eos and bool(finished.all()):
+            break
+        if step + 1 < max_new:
+            logits = advance(nxt)
+    return toks, scores, raw

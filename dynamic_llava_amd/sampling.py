@@ -78,6 +78,13 @@ def normalize_params(temperature=None, top_k=None, top_p=None):
     return t, k, p
 
 
+def eos_ids(kwargs, default):
+    """The only resolver of eos_token_id (request.py re-exports it): the ids as given (order, repeats), () for none.  `default` (the config's) stands in when the call names none; None means none."""
+    eos = kwargs.get("eos_token_id", default)
+    eos = eos if isinstance(eos, (list, tuple)) else (() if eos is None else (eos,))
+    return tuple(int(e) for e in eos)
+
+
 def device_route(kwargs, vocab_size, default_eos=None):
     """True when generate(**kwargs) samples on the device: do_sample=True with an integer `seed`, torch's RNG not asked for (`generator=`),
     a fresh cache, an EOS set the device can compare and a vocabulary the kernel takes.  Everything else keeps the route it had.
@@ -86,10 +93,7 @@ def device_route(kwargs, vocab_size, default_eos=None):
         return False
     if kwargs.get("past_key_values") is not None or int(vocab_size) > MAX_VOCAB:
         return False
-    eos = kwargs.get("eos_token_id", default_eos)
-    if isinstance(eos, (list, tuple)) and len(eos) > MAX_EOS_IDS:
-        return False
-    return True
+    return len(eos_ids(kwargs, default_eos)) <= MAX_EOS_IDS
 
 
 def masses(z, alive):
