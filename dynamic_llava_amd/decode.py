@@ -450,6 +450,33 @@ class DecodeScheduler:
         c.set_bounds(None, None)
         return c
 
+    def _fork_source(self, B, t_need):
+        """generate(num_return_sequences=n)'s prefill target: a second pooled cache, of the PROMPT batch B and without a decode reserve (nothing is ever decoded on it),
+        whose live rows dl_kv_fork copies into the B * n-row cache.  Made with it: the model-dtype [B, V] buffer of the prompts' last-position logits (_first_token)."""
+        cfg = self.config
+        c = self._fork_src_pool
+        if c is None or c.batch != B or c.t_cap < t_need or c.dtype != self.dtype or c.sparse_layer != cfg.sparse_config["sparse_layer"] or c.kv_format != self.kv_cache_format:
+            old_ptr = None if c is None else c.slab.data_ptr()
+            c = self._fork_src_pool = None
+            c = self._fork_src_pool = self._new_cache(B, -(-int(t_need) // 128) * 128)
+            self._fork_logits = torch.empty((B, cfg.vocab_size), dtype=self.dtype, device=self.device)
+            if old_ptr is not None:  # (the prefill graphs of forked requests hold both slabs' pointers, and their keys say so)
+                self._drop_graphs_on(old_ptr)
+        c.full_len_host = [0] * B
+        c.seen_tokens = 0
+        c.logical_cap = c.sparse_cap = int(t_need)
+        c.set_bounds(None, None)
+        return c
+
+    def _fork_host_mirrors(self, src, cache, n):
+        """The host mirrors of the B * n-row cache behind dl_kv_fork: every prompt's value n times (what _prefill_host_update left on the source)."""
+        cache.full_len_host = [v for v in src.full_len_host for _ in range(n)]
+        cache.seen_tokens = src.seen_tokens
+        cache.sparse_cap = cache.logical_cap - (src.logical_cap - src.sparse_cap)  # the same slots dropped from a larger reserve
+        cache.prefill_sparse_max = src.prefill_sparse_max
+        cache.set_bounds(None, None)
+        cache.sched_begin(max(cache.full_len_host), cache.prefill_sparse_max, self.decode_sync_every)
+
     def _drop_graphs_on(self, ptr):
         """Forget every captured prefill and decode step whose key holds the slab pointer `ptr`: the slab was freed, or handed to a caller who may free it."""
         self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if ptr not in k}
@@ -554,12 +581,22 @@ class DecodeScheduler:
         for _ in range(n_steps):
             g.replay()
 
-    def _first_token(self, st, x_last):
-        if st.use_gemv and x_last.dim() == 2 and x_last.is_contiguous():
+    def _first_token(self, st, x_last, fork=None):
+        """fork = (source cache, cache, n, host bound of the prompt lengths): generate(num_return_sequences=n) -- x_last holds the B prompts' last rows; their logits are computed at B rows, on the route a
+        plain call of B rows takes (the same bits), the prompts' K/V is forked into the B * n-row cache and every logits row repeated n times in front of the bookkeeping."""
+        logits, use_gemv = st.logits, st.use_gemv
+        if fork is not None:
+            cfg, logits = self.config, self._fork_logits
+            use_gemv = logits.shape[0] <= min(self.gemv_max_decode_batch, ops.gemv_max_batch(cfg.intermediate_size, self.dtype), ops.gemv_max_batch(cfg.hidden_size, self.dtype))  # _DecodeState.use_gemv at B rows
+        if use_gemv and x_last.dim() == 2 and x_last.is_contiguous():
             # up to three rows: the weight-streaming GEMV the decode steps use for the same matrix (41 vs 61 us for the library's skinny GEMM at B=1)
-            ops.gemv(self.lm_head.weight, st.logits, x=x_last)
+            ops.gemv(self.lm_head.weight, logits, x=x_last)
         else:
-            torch.matmul(x_last, self.lm_head.weight.t(), out=st.logits)
+            torch.matmul(x_last, self.lm_head.weight.t(), out=logits)
+        if fork is not None:
+            src, cache, n, max_len = fork
+            ops.kv_fork(src, cache, n, max_len=max_len)  # (the prompts' lengths are read on the device; max_len, the longest row the plan allows, sizes the grid)
+            st.logits.view(logits.shape[0], n, -1).copy_(logits[:, None, :].expand(-1, n, -1))
         self._prefill_logits_buf.copy_(st.logits)
         self._bookkeep(st, None)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits
 

@@ -130,6 +130,8 @@ SIGNATURES = {
     "dl_gumbel_hard_keep_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p]),
     "dl_gumbel_hard_keep_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_float, c_int, c_void_p]),
     "dl_kv_pack_rows": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int64, c_int64, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "dl_kv_fork": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                           c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
     "dl_prompt_layout": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_compact_rows_by_mask": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "dl_gemm_smallm_max_m": (c_int, []),
@@ -1354,6 +1356,37 @@ def kv_pack_rows(k_slab0, v_slab0, layer_stride, n_layers, keep, kv_len, T_cap):
                               keep.shape[1], d, dtype_code(k_slab0.dtype), _stream()),
         "dl_kv_pack_rows",
     )
+
+
+def kv_fork_arrays(src, dst, sparse_layer, n_rep, src_lens, dst_lens=None, max_len=None):
+    """dl_kv_fork on one storage array (include/dynllava.h).  src [L, 2, B, nKV, T_src, w] and dst [L, 2, B * n_rep, nKV, T_dst, w] of one element type, the last two
+    dimensions dense (the others may be those of a view); src_lens int32 [2, B] (dst_lens [2, B * n_rep], optional): rows of device memory, read / written on the
+    device.  max_len: host bound of the lengths (default: the smaller capacity)."""
+    _dev(src, dst, src_lens, dst_lens)
+    L, _, B, nKV, T_src, w = src.shape
+    T_dst, es = dst.shape[4], src.element_size()
+    assert src.dim() == 6 and dst.dim() == 6 and src.dtype == dst.dtype and src.shape[1] == 2 and tuple(dst.shape) == (L, 2, B * n_rep, nKV, T_dst, w), (tuple(src.shape), tuple(dst.shape), n_rep)
+    for t in (src, dst):
+        assert t.stride(5) == 1 and t.stride(4) == w
+    assert src_lens.dtype == torch.int32 and tuple(src_lens.shape) == (2, B) and src_lens.stride(1) == 1
+    assert dst_lens is None or (dst_lens.dtype == torch.int32 and tuple(dst_lens.shape) == (2, B * n_rep) and dst_lens.stride(1) == 1)
+    _check(
+        lib().dl_kv_fork(_p(src), _p(dst), *(src.stride(i) * es for i in range(4)), *(dst.stride(i) * es for i in range(4)), L, int(sparse_layer), B, int(n_rep), nKV, w * es,
+                         T_src, T_dst, _p(src_lens), src_lens.stride(0), _p(dst_lens), 0 if dst_lens is None else dst_lens.stride(0),
+                         min(T_src, T_dst) if max_len is None else int(max_len), _stream()),
+        "dl_kv_fork",
+    )
+
+
+def kv_fork(src_cache, dst_cache, n_rep, max_len=None):
+    """Fork a prefilled KV cache of B rows into one of B * n_rep rows (cache.KVSlabCache or KVSlabCacheMX8, both of one format): row b's live slots and its two
+    lengths go to rows b * n_rep .. b * n_rep + n_rep - 1.  One launch per storage array (the slab; with MXFP8 the scale bytes too); capturable."""
+    s, d = src_cache, dst_cache
+    if (s.kv_format, s.n_layers, s.sparse_layer, s.n_kv_heads, s.head_dim, s.batch * n_rep) != (d.kv_format, d.n_layers, d.sparse_layer, d.n_kv_heads, d.head_dim, d.batch) or n_rep < 1:
+        raise HipOpsError(f"kv_fork: a cache of {s.batch} rows x {n_rep} does not match the destination ({d.batch} rows), or the two differ in format / shape")
+    kv_fork_arrays(s.slab, d.slab, s.sparse_layer, n_rep, s.lens, d.lens, max_len)
+    if s.kv_format == "mxfp8":
+        kv_fork_arrays(s.scales, d.scales, s.sparse_layer, n_rep, s.lens, None, max_len)
 
 
 def prompt_layout(input_ids, n_feat, image_token, user_ids):

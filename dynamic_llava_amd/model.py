@@ -57,6 +57,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         self._mode = StepMode()
         self._prefill_graphs = {}
         self._prefill_pool = None
+        self._fork_src_pool = None  # generate(num_return_sequences=n): the B-row cache the prompts are prefilled into before dl_kv_fork (decode._fork_source)
         # captured prefill shapes kept (LRU).  288 GB of HBM: the graphs share one memory pool, an entry costs its static inputs (~0.7 MB of
         # pixels) and the graph object
         self.max_prefill_graphs = 64
@@ -265,6 +266,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if fmt != self.kv_cache_format:
             self.kv_cache_format = fmt
             self._cache_pool = None
+            self._fork_src_pool = None
             self._dstate = None
             self._prefill_graphs = {}
         return self
@@ -425,6 +427,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
             "device_logits_processors": True,  # repetition_penalty / no_repeat_ngram_size / bad_words_ids act inside the captured graphs (dl_logits_process)
             "device_logprobs": True,  # generate(output_logprobs=True, top_logprobs=n) reads the log-probabilities off inside the captured graphs (dl_decode_logprobs)
+            "device_fork": True,  # generate(do_sample=True, seed=..., num_return_sequences=n) prefills a prompt once and forks its K/V into n decode rows (dl_kv_fork)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
         }
@@ -534,7 +537,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call.
         output_logprobs / top_logprobs: logprobs.reference_rows on every step's raw fp32 logits (the rule dl_decode_logprobs implements), masked behind a row's EOS."""
         req = request.parse(kwargs, self.config)
-        out = self.forward(inputs.to(self.device), attention_mask=req.attention_mask, images=images, image_features=req.image_features)
+        attention_mask, image_features = req.attention_mask, req.image_features
+        if req.n_return > 1:  # n answers per prompt on a host route: every prompt n times in the batch (rows b * n .. b * n + n - 1, HF's order), no fork
+            rep = lambda t: t.repeat_interleave(req.n_return, dim=0) if torch.is_tensor(t) else t
+            inputs, images, attention_mask, image_features = rep(inputs), rep(images), rep(attention_mask), rep(image_features)
+        out = self.forward(inputs.to(self.device), attention_mask=attention_mask, images=images, image_features=image_features)
         cache = out.past_key_values
         max_new = req.max_new(cache.full_len_host)
         # last VALID position of every row: the logits are right-padded with zeros when rows differ in length; the last layer's KV length is the (compacted) row length
@@ -627,6 +634,12 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         sample_row_base=<int> offsets the rows' random streams for sharded batches); without seed, or with generator=, through
         _generate_sample on torch's RNG), num_beams(1), use_cache(True), eos_token_id, pad_token_id, attention_mask,
         return_dict_in_generate (+ output_scores), image_features (pre-computed projector output, testing),
+        num_return_sequences=n (n sampled answers per prompt; needs do_sample=True): `sequences` is [B * n, T] with prompt b's answers in rows b * n .. b * n + n - 1 (HF's
+        order), and every per-row result (scores, logits, logprobs, top_logprobs, top_logprob_ids, the returned cache) has B * n rows.  With seed=<int> the B prompts are
+        prefilled ONCE, at batch B exactly as a plain call of them would be, and inside the captured prefill graph dl_kv_fork copies every prompt's live K/V into its n decode
+        rows; row b * n + r draws with the random stream of row sample_row_base + b * n + r (a sharded batch passes sample_row_base = its first global prompt * n), so the
+        n first tokens already differ.  On the host routes (generator=, no seed, past the device caps) the prompts are repeated n times in the batch instead.  n > 1 without
+        do_sample or in score() raises ValueError, with past_key_values NotImplementedError, before any launch,
         repetition_penalty / no_repeat_ngram_size / bad_words_ids (HF's RepetitionPenalty / NoRepeatNGram / NoBadWords logits processors, bit for bit, on the
         tokens generated in this call -- the prompt is never part of the history, as for HF driven by inputs_embeds; on the device inside the same captured
         graphs (dl_logits_process; the rule is logits_rules.py), in front of the EOS ban of min_new_tokens and of temperature / top_k / top_p; a request past
@@ -658,12 +671,17 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             tm["ev"][0].record()
         lay, dev_layout = self._generate_layout(inputs, req, self._n_feat(images, req.image_features))
         lens, B, max_new = lay["lens"], lay["B"], req.max_new(lay["lens"])
-        cache = self._pooled_cache(B, max(lens) + max_new + 1)
+        # num_return_sequences = n > 1: the B prompts are prefilled once, into a source cache of B rows; inside the prefill closure dl_kv_fork copies every prompt's live
+        # K/V into n rows of the B * n-row cache and the first-step logits are repeated, so the n rows of a prompt draw n first tokens (row b * n + r: Philox counter row
+        # row_base + b * n + r).  Everything behind the prefill serves a B * n-row state as it serves any batch
+        n = req.n_return
+        cache = self._pooled_cache(B * n, max(lens) + max_new + 1)
+        fork = None if n == 1 else (self._fork_source(B, max(lens) + 1), n)
         self._rope_tables(max(lens) + max_new + 1)
-        st = self._get_dstate(B, max_new)
+        st = self._get_dstate(B * n, max_new)
         self._bind_schedule(st, cache)
         self._arm(st, req, max_new)
-        ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new)
+        ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new, fork)
         self.last_prefill_logits = self._prefill_logits_buf
         if tm is not None:
             tm["ev"][1].record()
@@ -673,7 +691,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if on_step is not None:
             on_step(0)
         produced = self._decode_loop(st, cache, max_new, req.sync_every, on_step)
-        if B == 1 or self._lp_ws is not None:
+        if B * n == 1 or self._lp_ws is not None:
             self.check_device_errors()  # (B > 1 too: dl_linear_packed's k ranges hand over in-kernel, through _lp_err; generate() is about to synchronise for its result anyway)
         if dev_layout and int(ent["didx"]["err"].item()) != 0:
             # a row without exactly one image token (text-only row, several images): what was computed is meaningless -- repeat the

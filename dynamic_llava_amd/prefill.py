@@ -523,7 +523,7 @@ class PrefillEngine:
             raise NotImplementedError("multi-token forward on a non-empty cache (new-instruct round, DML:2506-2521) is SURVEY 8f row N2")
         self._rope_tables(max(lens) + reserve)
         x = self._prefill_run(p, embeds, cache, indices, last_only)
-        if cache.kv_format == "mxfp8" and cache is not getattr(self, "_cache_pool", None):
+        if cache.kv_format == "mxfp8" and cache is not getattr(self, "_cache_pool", None) and cache is not getattr(self, "_fork_src_pool", None):
             cache.release_scratch()  # (a cache forward() hands to its caller: no captured graph holds the scratch's pointer -- those live on the pooled cache, which keeps it)
         self._prefill_host_update(p, cache, indices)
         if p["instruct_drop"]:
@@ -571,16 +571,21 @@ class PrefillEngine:
         return dict(sig=("dev", Bq, Wb, n_feat), B=Bq, lens=[n_row] * Bq, lens_bucket=[n_row_b] * Bq, indices=fake, text_src=[0], text_dst=[0], img_dst=[0], img_rows=list(range(Bq)),
                     total=Bq * n_row_b, n_feat=n_feat, width=Wq, bucket=Wb), True
 
-    def _generate_prefill(self, lay, dev_layout, inputs, images, image_features, cache, st, max_new):
+    def _generate_prefill(self, lay, dev_layout, inputs, images, image_features, cache, st, max_new, fork=None):
         """generate()'s prefill, the first token's bookkeeping launch included -> (entry of _prefill_graphs, path: "eager" on a shape's first sighting, then
-        "graph-capture", then "graph-replay"); a model that cannot be captured (use_hip_graph off, debug_records, hooks) keeps no entry: (None, "eager")."""
+        "graph-capture", then "graph-replay"); a model that cannot be captured (use_hip_graph off, debug_records, hooks) keeps no entry: (None, "eager").
+        fork = (source cache, n) (num_return_sequences = n > 1): the prompts are prefilled into the source cache, at their own batch, and forked into `cache`'s B * n rows
+        in front of the first token's launch (_first_token) -- inside the same closure, so inside the captured graph."""
         lens, indices, B, n_feat = lay["lens"], lay["indices"], lay["B"], lay["n_feat"] if dev_layout else None
+        target = cache if fork is None else fork[0]  # the cache the prefill writes
         vp = getattr(self.model, "image_score_predictor", None)
         if not (self.use_hip_graph and self.debug_records is None) or (vp is not None and (len(vp._forward_hooks) or len(vp._forward_pre_hooks))):  # not capturable
             f = image_features if image_features is not None else (self.encode_images(images) if images is not None else None)
             embeds = self._assemble(lay, self._dev_idx(lay), inputs, f)
-            x, _, _, _ = self._prefill(embeds, lens, indices, cache, reserve=max_new + 1, last_only=True)
-            self._first_token(st, x)
+            x, _, _, _ = self._prefill(embeds, lens, indices, target, reserve=max_new + 1, last_only=True)
+            self._first_token(st, x, None if fork is None else (target, cache, fork[1], max(lens)))
+            if fork is not None:
+                self._fork_host_mirrors(target, cache, fork[1])
             return None, "eager"
         # ADVICE r3: the instruct predictor's compaction span is baked into the captured plan, and `sig` ignores token values: two
         # equally long multi-turn prompts whose last "USER:" sits elsewhere must not share a graph
@@ -588,6 +593,8 @@ class PrefillEngine:
         key = (lay["sig"], None if images is None else tuple(images.shape), None if image_features is None else tuple(image_features.shape),
                cache.slab.data_ptr(), cache.t_cap, self._rope[0].data_ptr(), self._mode, repr(self.config.sparse_config), li_key,
                self._prefill_knob_key(), self._kv_format_key(cache))  # (a knob toggled at run time must not replay a graph captured under the other setting)
+        if fork is not None:  # the graph holds both caches' pointers (_drop_graphs_on looks for either slab's among the key's elements)
+            key += (fork[1], target.slab.data_ptr(), target.t_cap, self._kv_format_key(target), self._fork_logits.data_ptr())
         ent = self._prefill_graphs.get(key)
         path = "eager" if ent is None else ("graph-capture" if ent["graph"] is None else "graph-replay")
         if ent is None:
@@ -609,15 +616,15 @@ class PrefillEngine:
             else:
                 ent["didx"] = self._dev_idx(lay)
 
-            def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st):
+            def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st, target=target, fork=fork):
                 if dev_layout:
                     p_ = ent["plan"]  # the plan's shapes are the bucket's; its device metadata is (re)written here at the true width
                     ops.prompt_layout_into(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS, ent["didx"], w_true=ent["w_true"], n_drop=(p_["n_img"] - p_["k"]) if p_["vision_on"] else 0,
                                            cu=p_["cu"], cu2=p_["cu2"], lens=p_["lens_dev"], last_rows=p_["last_rows"])
                 f = ent["feats"] if ent["feats"] is not None else (self.encode_images(ent["images"]) if ent["images"] is not None else None)
                 emb = self._assemble(lay, ent["didx"], ent["ids"], f)
-                x = self._prefill_run(ent["plan"], emb, cache, copy.deepcopy(ent["indices"]), True)
-                self._first_token(st, x)
+                x = self._prefill_run(ent["plan"], emb, target, copy.deepcopy(ent["indices"]), True)
+                self._first_token(st, x, None if fork is None else (target, cache, fork[1], ent["plan"]["max_len"]))
 
             ent["run"] = run
             self._prefill_graphs[key] = ent
@@ -652,7 +659,9 @@ class PrefillEngine:
         if dev_layout and lay["bucket"] != lay["width"]:  # host mirrors follow the true lengths, not the bucket's
             drop_ = (p_host["n_img"] - p_host["k"]) if p_host["vision_on"] else 0
             p_host = dict(p_host, lens=list(lens), lens2=[n - drop_ for n in lens] if self.config.sparse_config["sparse_layer"] < self.config.num_hidden_layers else list(lens))
-        self._prefill_host_update(p_host, cache, indices)
+        self._prefill_host_update(p_host, target, indices)
+        if fork is not None:
+            self._fork_host_mirrors(target, cache, fork[1])
         return ent, path
 
     def _unpad_embeds(self, inputs_embeds, attention_mask, input_embeds_indices):

@@ -25,6 +25,23 @@ def route(kwargs, rules, vocab_size, default_eos) -> str:
     return "device"
 
 
+def return_sequences(kwargs) -> int:
+    """num_return_sequences, validated: n sampled answers per prompt.  None and 1 are the request without the keyword; n > 1 needs do_sample (HF's rule: greedy
+    search returns one sequence), and is not built for score() nor on a caller's cache."""
+    n = kwargs.get("num_return_sequences")
+    if n is None:
+        return 1
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError(f"num_return_sequences must be an int >= 1 (got {n!r})")
+    if n > 1 and not kwargs.get("do_sample", False):
+        raise ValueError(f"num_return_sequences={n} needs do_sample=True: greedy search returns one sequence per prompt")
+    if n > 1 and kwargs.get("_score_labels") is not None:
+        raise ValueError("score() takes no num_return_sequences: a label sequence is scored once")
+    if n > 1 and kwargs.get("past_key_values") is not None:
+        raise NotImplementedError("num_return_sequences > 1 on generate(past_key_values=...) is not built: the fork follows a prefill")
+    return n
+
+
 @dataclass(frozen=True)
 class Request:
     """Everything generate() and its host routes read from **kwargs."""
@@ -49,6 +66,7 @@ class Request:
     route: str
     max_new_tokens: Optional[int]
     max_length: Optional[int]
+    n_return: int = 1  # num_return_sequences: sampled answers per prompt, rows b * n .. b * n + n - 1 of every per-row result
 
     def max_new(self, lens) -> int:
         """The number of steps: max_new_tokens, or max_length - the longest prompt (HF's default: 20 steps)."""
@@ -62,7 +80,7 @@ class Request:
 
 def parse(kwargs, config, sync_every=None) -> Request:
     """generate()'s **kwargs -> Request.  Every keyword is validated here, before any device work, in this order: the logits processors, score() with
-    processors, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), the sampling parameters."""
+    processors, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences, the sampling parameters."""
     V, eos = config.vocab_size, eos_ids(kwargs, config.eos_token_id)
     rules = logits_rules.normalize(kwargs, V, eos)  # (a one-token bad word equal to an EOS id is dropped, as in HF)
     forced = kwargs.get("_score_labels")
@@ -73,6 +91,7 @@ def parse(kwargs, config, sync_every=None) -> Request:
         raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
     if (kwargs.get("num_beams", 1) or 1) != 1:
         raise NotImplementedError("beam search is not built (harness default num_beams=1)")
+    n_return = return_sequences(kwargs)
     rt, sampled = route(kwargs, rules, V, config.eos_token_id), None
     if kwargs.get("do_sample", False) and sampling.device_route(kwargs, V, config.eos_token_id):
         # seed=<int>: the draw moves into the captured graphs (device data, in no graph key).  Validated whatever the route: processors past the device caps still send it to the host loop
@@ -82,7 +101,7 @@ def parse(kwargs, config, sync_every=None) -> Request:
                    temperature=float(kwargs.get("temperature", 1.0) or 1.0), top_k=int(kwargs.get("top_k", 0) or 0), top_p=None if top_p is None else float(top_p),
                    generator=kwargs.get("generator"), want_dict=want_dict, want_scores=want_dict and bool(kwargs.get("output_scores")), want_logits=want_dict and bool(kwargs.get("output_logits")),
                    sync_every=sync_every if kwargs.get("sync_every") is None else int(kwargs["sync_every"]), forced=forced, attention_mask=kwargs.get("attention_mask"),
-                   image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"))
+                   image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"), n_return=n_return)
 
 
 def host_loop(logits, advance, req: Request, max_new: int, greedy: bool):

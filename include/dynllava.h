@@ -354,6 +354,23 @@ int dl_kv_pack_rows(void* k_slab0, void* v_slab0, int64_t layer_stride, int n_la
                     int T_cap, const int32_t* keep, const int32_t* kv_len, int B, int n_kv_heads, int T, int head_dim, int dtype,
                     void* stream);
 
+/* ---- length-aware, replicated copy of a KV slab: the fork of generate(num_return_sequences=n) between ONE prefill of B_src prompts and the decode of
+ * B_src * n_rep sampled answers.  Everything is in BYTES, so the one entry serves every storage: row_bytes = bytes of one slot of one head (2 d for a
+ * 16-bit slab, 4 d for fp32, d for MXFP8 codes, d / 32 for their scales); the four strides of src and of dst are those of (layer, K/V plane, batch
+ * row, kv head); the live slots of a (row, head) are one contiguous span.  For layer l with group g = (l >= sparse_layer), plane p, source row b, head
+ * h: the first min(src_lens[g * src_lens_stride + b], src_T_cap, dst_T_cap, max_len) * row_bytes bytes of the source (b, h) plane are written to the
+ * same offsets of the destination rows b * n_rep + r, r < n_rep (each source chunk read once, stored n_rep times).  No other byte of dst is written.
+ * dst_lens (may be NULL; int32, group stride dst_lens_stride): dst_lens[g][b * n_rep + r] = src_lens[g][b] for both groups, one plain store each.
+ * The lengths are read on the device (a negative one counts as 0); max_len is a host bound that only sizes the grid -- no host sync, no workspace, no
+ * atomics: capturable.  n_rep = 1 is a plain live-length copy.  Accesses are 16 bytes wide where both bases and all eight strides are multiples of
+ * 16, else the widest power of two they share (down to single bytes); a span's tail goes byte by byte.  src and dst must not overlap.
+ * DL_ERR_ARG: NULL src / dst / src_lens, n_rep / B_src / row_bytes / n_kv_heads / n_layers < 1, sparse_layer outside [0, n_layers], a negative
+ * stride, capacity or max_len, more than 65535 (row, head) pairs. */
+int dl_kv_fork(const void* src, void* dst, int64_t src_stride_l, int64_t src_stride_p, int64_t src_stride_b, int64_t src_stride_h, int64_t dst_stride_l,
+               int64_t dst_stride_p, int64_t dst_stride_b, int64_t dst_stride_h, int n_layers, int sparse_layer, int B_src, int n_rep, int n_kv_heads,
+               int row_bytes, int src_T_cap, int dst_T_cap, const int32_t* src_lens, int64_t src_lens_stride, int32_t* dst_lens, int64_t dst_lens_stride,
+               int max_len, void* stream);
+
 /* ---- prefill compaction of the instruct predictor (DML:2261-2375: `torch.where` on the keep decisions of the last instruct turn + gather/cat)
  * without a device->host copy.  ONE packed sequence of `total` rows [total, H]; rows [span0, span0 + n_span) survive where decision[j] != 0,
  * all other rows always.  h_out [total, H] / pos_out [total] receive the kept rows in order (pos_in NULL: the position is the row index);
