@@ -24,12 +24,13 @@ class StepMode:
     forced: bool = False  # dl_decode_score: score() -- score the label, feed the label
     processed: bool = False  # dl_logits_process in front of the kernel; an all-neutral request is exactly the request without the keywords
     logprobs: int = -1  # dl_decode_logprobs behind the kernel: generate(output_logprobs=True, top_logprobs=n) -- -1: off, else n
+    stop: bool = False  # dl_decode_stop as the last launch: generate(stop_sequences= / stopping_criteria=[keyword criterion]); the list itself is device data
 
     @classmethod
     def of(cls, req, max_new):
         """The mode of a parsed request (request.Request) of max_new steps; the one place the EOS tuple becomes the kernels' -1 / id / tuple."""
         return cls(eos=-1 if not req.eos else (req.eos[0] if len(req.eos) == 1 else req.eos), pad=req.pad, min_new=min(req.min_new, max_new), sampled=req.sampled is not None,
-                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp)
+                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp, stop=bool(req.stops))
 
 
 class _DecodeState:
@@ -106,6 +107,10 @@ class _DecodeState:
         # dl_decode_logprobs' outputs (generate(output_logprobs=True)): made by need_logprobs() on the first such request -- a model that never asks keeps its
         # footprint -- and with the state thereafter; slot j belongs to step j, like out_ids
         self.lp = self.top_lp = self.top_ids = None
+        # dl_decode_stop's table (generate(stop_sequences=)): device memory the captured launch reads, rewritten by generate() before the first launch of such a
+        # request, like sample_params -- one graph serves every stop list
+        self.stop_table = ops.stop_table_block(device)
+        self.tok_host = None  # generate(streamer=): ring of pinned token words beside obs_host, made by need_stream() on the first such request
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
         self.tp_gran = ops.gemv_gu_tp_workspace(tpm.d_model, device) if (B == 1 and tpm is not None and dtype in (torch.bfloat16, torch.float16) and H <= 5120 and H % 8 == 0 and tpm.d_model % 32 == 0) else None
@@ -136,6 +141,12 @@ class _DecodeState:
             self.lp = torch.zeros((B, cap), dtype=torch.float32, device=dev)
             self.top_lp = torch.zeros((B, cap, MAX_TOP_LOGPROBS), dtype=torch.float32, device=dev)
             self.top_ids = torch.full((B, cap, MAX_TOP_LOGPROBS), -1, dtype=torch.int64, device=dev)
+
+
+    def need_stream(self, chunk):
+        """The pinned ring the chunks' tokens leave through (generate(streamer=)): 4 slots of B x chunk int64 words, one per observation in flight."""
+        if self.tok_host is None or self.tok_host.shape[1] < self.B * chunk:
+            self.tok_host = torch.empty((4, self.B * chunk), dtype=torch.int64).pin_memory()
 
 
 @contextlib.contextmanager
@@ -202,6 +213,8 @@ class DecodeScheduler:
             ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
         if m.logprobs >= 0:  # generate(output_logprobs=True): the committed token's log-probability on the step's RAW logits (slot step - 1)
             ops.decode_logprobs(st.logits, st.cur_ids, st.step, st.lp, m.logprobs, st.top_lp, st.top_ids)
+        if m.stop:  # generate(stop_sequences=): a row whose tokens now end in a stop sequence is finished, as by an EOS token -- the last launch, so all above see today's flags
+            ops.decode_stop(st.out_ids, st.step, st.finished, st.stop_table)
 
     def _use_tp(self):
         """The output text predictor decides in the decode step (it sits in front of a layer that exists)."""
@@ -498,6 +511,8 @@ class DecodeScheduler:
         if req.rules.on:
             st.logits_params.copy_(ops.logits_params_words(req.rules.repetition_penalty, req.rules.no_repeat_ngram_size, len(req.rules.bad_words)))
             st.bad_words.copy_(ops.bad_words_table(req.rules.bad_words, "cpu"))
+        if req.stops:
+            st.stop_table.copy_(ops.stop_table_words(req.stops))
         if req.forced is not None:
             st.labels.fill_(IGNORE_INDEX)
             st.labels[:, : req.forced.shape[1]].copy_(req.forced)
@@ -600,16 +615,20 @@ class DecodeScheduler:
         self._prefill_logits_buf.copy_(st.logits)
         self._bookkeep(st, None)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits
 
-    def _decode_loop(self, st, cache, max_new, sync_every, on_step=None):
+    def _decode_loop(self, st, cache, max_new, sync_every, on_step=None, feed=None):
         """generate()'s decode loop behind the first token: chunks of captured steps, scheduled from the lengths the predictor actually leaves (DML:2377-2391,
         CU:153-164) -> the number of tokens produced (the first included).  on_step(j), when given, runs after step j: the steps are then enqueued one by one
         (the caller reads the step buffer after each); the schedule (chunks, bounds) is the same.  Before a chunk the host knows the un-evicted group's length
         exactly, and the evicted group's as OBSERVED after an earlier chunk (non-blocking copy into pinned memory, consumed one chunk late so that the host never
         waits for steps it has just enqueued) plus the steps enqueued since.  Those bounds pick the split-KV factor / the fused q|k|v+attention launch
-        (cache.n_splits), i.e. which captured graph is replayed; the values are data, never timing, so the schedule is deterministic for a given request."""
-        B, has_eos = st.B, self._mode.eos != -1
+        (cache.n_splits), i.e. which captured graph is replayed; the values are data, never timing, so the schedule is deterministic for a given request.
+        feed (stopping.Feed, generate(streamer=)): a chunk's tokens travel with its observation -- one more non-blocking copy into pinned memory in front of the same
+        event -- and are pushed when that observation is consumed; the chunks, the bounds and what is replayed do not change."""
+        B, has_eos = st.B, self._mode.eos != -1 or self._mode.stop  # (a stop sequence ends a row as an EOS id does)
         stops = has_eos or self._mode.forced  # (score(): finished = labels exhausted)
-        produced, chunks, pending = 1, 0, []  # pending: (ring slot, produced-when-copied)
+        produced, chunks, pending = 1, 0, []  # pending: (ring slot, produced-when-copied, tokens in the chunk)
+        if feed is not None:
+            st.need_stream(max(1, int(sync_every)))
         cache.sched_begin(max(cache.full_len_host), getattr(cache, "prefill_sparse_max", None) or max(cache.full_len_host), sync_every)
         while produced < max_new:
             # EOS of a short answer (VQA: a few tokens) must not cost two chunks of wasted steps: the first chunks' flags are read blocking (one
@@ -617,9 +636,11 @@ class DecodeScheduler:
             keep_newest = 0 if (has_eos and chunks <= 2) else 1
             all_done = False
             while len(pending) > keep_newest:
-                slot, at = pending.pop(0)
+                slot, at, n_tok = pending.pop(0)
                 st.obs_ev[slot].synchronize()
                 row = st.obs_host[slot]
+                if feed is not None:
+                    feed.push(st.tok_host[slot, : B * n_tok].view(B, n_tok).clone())
                 cache.sched_observe(at, int(row[B : 2 * B].max()))
                 all_done = all_done or (stops and int(row[2 * B :].min()) != 0)
             if all_done:
@@ -639,6 +660,8 @@ class DecodeScheduler:
                 st.obs_host[slot, : 2 * B].copy_(cache.lens.view(-1), non_blocking=True)
                 if stops:
                     st.obs_host[slot, 2 * B :].copy_(st.finished, non_blocking=True)
+                if feed is not None:
+                    st.tok_host[slot, : B * n].view(B, n).copy_(st.out_ids[:, produced - n : produced], non_blocking=True)
                 st.obs_ev[slot].record()
-                pending.append((slot, produced))
+                pending.append((slot, produced, n))
         return produced

@@ -173,6 +173,7 @@ SIGNATURES = {
     ),
     "dl_logits_process": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_decode_logprobs": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dl_decode_stop": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -979,6 +980,40 @@ def decode_logprobs(logits, next_ids, step, logprobs, n_top=0, top_logprobs=None
         "dl_decode_logprobs",
     )
     return logprobs
+
+
+STOP_TABLE_WORDS = 8 + 8 * 9  # dl_stop_table (include/dynllava.h): n_stops, 7 reserved words, then DL_STOP_MAX_SEQS rows of a length and DL_STOP_MAX_LEN ids
+
+
+def stop_table_words(stops=()):
+    """dl_stop_table (include/dynllava.h) as a CPU int32 [STOP_TABLE_WORDS] tensor: copy it into the device block (`stop_table_block`) before the first launch of
+    a request.  stops: up to 8 sequences of 1..8 token ids (stopping.normalize's, within stopping.MAX_STOPS / MAX_STOP_LEN)."""
+    if len(stops) > 8 or any(not 1 <= len(s) <= 8 for s in stops):
+        raise HipOpsError(f"stop_table_words: {len(stops)} sequences of up to {max((len(s) for s in stops), default=0)} tokens: dl_decode_stop takes 8 of 1..8")
+    t = torch.zeros(STOP_TABLE_WORDS, dtype=torch.int32)
+    t[0] = len(stops)
+    for i, s in enumerate(stops):
+        t[8 + 9 * i] = len(s)
+        t[9 + 9 * i : 9 + 9 * i + len(s)] = torch.tensor([int(v) for v in s], dtype=torch.int32)
+    return t
+
+
+def stop_table_block(device):
+    """The device block dl_decode_stop reads (an empty list: the launch writes nothing)."""
+    return stop_table_words(()).to(device)
+
+
+def decode_stop(out_ids, step, finished, table):
+    """Stop sequences behind the step-closing launch (include/dynllava.h, stopping.py): a row that is not finished and whose step[b] tokens out_ids[b, :step[b]] end in
+    one of the table's sequences gets finished[b] = 1; nothing else is written.  out_ids int64 [B, cap]; step, finished int32 [B]; table: int32
+    [STOP_TABLE_WORDS] on the device (stop_table_words)."""
+    _dev(out_ids, step, finished, table)
+    assert out_ids.dtype == torch.int64 and out_ids.dim() == 2 and out_ids.is_contiguous()
+    B, cap = out_ids.shape
+    assert step.dtype == torch.int32 and step.numel() == B and step.is_contiguous() and finished.dtype == torch.int32 and finished.numel() == B and finished.is_contiguous()
+    assert table.dtype == torch.int32 and table.numel() >= STOP_TABLE_WORDS and table.is_contiguous()
+    _check(lib().dl_decode_stop(_p(out_ids), int(cap), int(B), _p(step), _p(finished), _p(table), _stream()), "dl_decode_stop")
+    return finished
 
 
 def logits_params_words(repetition_penalty=1.0, no_repeat_ngram_size=0, n_bad_words=0):

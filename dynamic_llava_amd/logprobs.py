@@ -102,15 +102,30 @@ def mask_after_eos(sequences, eos_ids, logprobs, top_logprobs=None, top_ids=None
     return logprobs, top_logprobs, top_ids
 
 
-def host_result(step_logits, sequences, eos_ids, n):
+def mask_after_columns(finish, logprobs, top_logprobs=None, top_ids=None):
+    """mask_after_eos for rows that can also finish on a stop sequence or a stopping criterion: in place, the columns BEHIND column finish[b] of row b report
+    0.0 / -1; the finishing token's own entry stays.  finish: int64 [B] (stopping.finish_columns; T or more where the row never finishes)."""
+    after = torch.arange(logprobs.shape[1], dtype=torch.int64, device=logprobs.device)[None, :] > finish.to(logprobs.device)[:, None]
+    logprobs.masked_fill_(after, 0.0)
+    if top_logprobs is not None:
+        top_logprobs.masked_fill_(after[..., None], 0.0)
+    if top_ids is not None:
+        top_ids.masked_fill_(after[..., None], -1)
+    return logprobs, top_logprobs, top_ids
+
+
+def host_result(step_logits, sequences, eos_ids, n, finish=None):
     """The host routes of generate(): the rule on every step's raw fp32 logits (a sequence of [B, V], one per column of `sequences`), masked ->
-    the result keys on sequences' device."""
+    the result keys on sequences' device.  finish: the rows' finish columns when they can finish on more than EOS (mask_after_columns), else None."""
     B, T = sequences.shape
     lp, top_lp, top_ids = torch.zeros((B, T), dtype=torch.float32), torch.zeros((B, T, n), dtype=torch.float32), torch.full((B, T, n), -1, dtype=torch.int64)
     seq = sequences.detach().cpu()
     for t in range(T):
         lp[:, t], top_lp[:, t], top_ids[:, t] = reference_rows(step_logits[t], seq[:, t], n)
-    mask_after_eos(seq, eos_ids, lp, top_lp, top_ids)
+    if finish is None:
+        mask_after_eos(seq, eos_ids, lp, top_lp, top_ids)
+    else:
+        mask_after_columns(finish.cpu(), lp, top_lp, top_ids)
     dev = sequences.device
     out = {"logprobs": lp.to(dev)}
     if n > 0:

@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import logprobs, request, sampling, scoring
+from . import logprobs, request, sampling, scoring, stopping
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -427,6 +427,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             "device_sampling": True,  # generate(do_sample=True, seed=...) draws inside the captured graphs (dl_decode_sample)
             "device_logits_processors": True,  # repetition_penalty / no_repeat_ngram_size / bad_words_ids act inside the captured graphs (dl_logits_process)
             "device_logprobs": True,  # generate(output_logprobs=True, top_logprobs=n) reads the log-probabilities off inside the captured graphs (dl_decode_logprobs)
+            "device_stop_sequences": True,  # generate(stop_sequences= / stopping_criteria=[keyword criterion]) finishes rows inside the captured graphs (dl_decode_stop)
             "device_fork": True,  # generate(do_sample=True, seed=..., num_return_sequences=n) prefills a prompt once and forks its K/V into n decode rows (dl_kv_fork)
             "test_hook_force_text_decision": self.force_text_decision is not None, "test_hook_single_split_keys_override": self.single_split_keys_override,
             "test_hook_min_keys_per_split": getattr(self, "min_keys_per_split", None),
@@ -551,7 +552,9 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
     def _host_decode(self, req, cache, logits, max_new, greedy):
         """A host route behind its first forward(): request.host_loop over single decode steps on `cache` -> the tokens [B, T_new], or generate()'s dict."""
         self.last_prefill_logits = logits.clone()
-        toks, scores, raw = request.host_loop(logits, lambda nxt: self.forward(nxt[:, None], past_key_values=cache).logits[:, -1].float(), req, max_new, greedy)
+        finish = []  # the rows' finish columns, asked for only where a row can finish on more than EOS
+        more = dict(finish=finish) if (req.stops or req.criteria) else {}
+        toks, scores, raw = request.host_loop(logits, lambda nxt: self.forward(nxt[:, None], past_key_values=cache).logits[:, -1].float(), req, max_new, greedy, **more)
         seq, self.last_cache = torch.stack(toks, dim=1), cache
         if not req.want_dict:
             return seq
@@ -559,7 +562,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         if req.want_scores:
             res["scores"] = tuple(scores)
         if req.n_lp >= 0:
-            res.update(logprobs.host_result(raw, seq, req.eos, req.n_lp))
+            res.update(logprobs.host_result(raw, seq, req.eos, req.n_lp, finish[0] if (req.stops or req.criteria) else None))
         return res
 
     @torch.no_grad()
@@ -652,7 +655,19 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         device inside the same captured graphs (dl_decode_logprobs behind the step-closing launch; the rule is logprobs.py): no [B, V] tensor reaches the host and
         the decode loop keeps its chunks.  Columns after a row's first EOS (pad in `sequences`) hold 0.0 / -1, the EOS token's own entry is real; the host routes
         (_generate_sample, _generate_on_cache) return the same keys from the same rule.  Bad values raise ValueError before any launch.
-        Still ignored without a word: streamer, stopping_criteria, logits_processor, suppress_tokens, sequence_bias.
+        stop_sequences=[ids, ...] (non-empty lists of token ids or 1-D integer tensors) and stopping_criteria=[...] (a list or HF StoppingCriteriaList): a row finishes
+        when the tokens generated in this call end in a stop sequence -- the token-tail rule of the reference's KeywordsStoppingCriteria (llava/mm_utils.py:257-267),
+        per row; an item of stopping_criteria with a `keyword_ids` attribute contributes its sequences (its decoded-text substring check needs a tokenizer and is not
+        built).  The matched tokens stay in `sequences`, pad follows, and the result is trimmed where the last row finishes, exactly as for EOS; min_new_tokens does
+        not hold a match back; `logprobs` / `top_logprobs` report 0.0 / -1 behind it.  Up to stopping.MAX_STOPS sequences of up to stopping.MAX_STOP_LEN tokens are
+        matched on the device inside the same captured graphs (dl_decode_stop behind the step-closing launch; the rule is stopping.py; the list is device data, one
+        graph serves every list); a longer list, and any other item of stopping_criteria -- a callable (ids [B, t], scores [B, V]) -> bool | BoolTensor [B], called
+        once per step on the tokens generated in this call -- runs the plain loop over forward() with the same rule.  Bad values raise ValueError before any launch.
+        streamer= (any object with put(tensor) and end(), e.g. HF's TextStreamer / TextIteratorStreamer), on every route: put(an empty int64 CPU tensor [B, 0])
+        first, then put(sequences[:, j].cpu()) for every column of the returned `sequences`, in order and once each, then end().  On the device route the first
+        token is put after the prefill and a chunk's tokens when the loop consumes that chunk's observation (the same pinned, non-blocking copies; the schedule,
+        the tokens and the captured graphs are those of the call without a streamer); sync_every=1 is the knob for token-by-token latency.
+        Still ignored without a word: logits_processor, suppress_tokens, sequence_bias.
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
         the new token ids / pixels into static buffers."""
@@ -690,7 +705,14 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         on_step = (lambda j: self._score(req, st, j, scores, raw_logits)) if (req.want_scores or req.want_logits) else None
         if on_step is not None:
             on_step(0)
-        produced = self._decode_loop(st, cache, max_new, req.sync_every, on_step)
+        feed = None
+        if req.streamer is not None:
+            if dev_layout and int(ent["didx"]["err"].item()) != 0:  # (the check below, made before a token of a meaningless run reaches the streamer)
+                ent["didx"]["err"].zero_()
+                return self.generate(inputs, images=images, image_sizes=image_sizes, _host_layout=True, **kwargs)
+            feed = stopping.Feed(req.streamer, B * n, req.eos, req.stops)
+            feed.push(st.out_ids[:, :1].cpu())  # the first token: the caller waits for it
+        produced = self._decode_loop(st, cache, max_new, req.sync_every, on_step, feed)
         if B * n == 1 or self._lp_ws is not None:
             self.check_device_errors()  # (B > 1 too: dl_linear_packed's k ranges hand over in-kernel, through _lp_err; generate() is about to synchronise for its result anyway)
         if dev_layout and int(ent["didx"]["err"].item()) != 0:
@@ -698,7 +720,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             # call with the host-side layout, which handles (or rejects) those rows like the reference does
             ent["didx"]["err"].zero_()
             return self.generate(inputs, images=images, image_sizes=image_sizes, _host_layout=True, **kwargs)
-        return self._finish(req, st, cache, produced, scores, raw_logits, tm)
+        res = self._finish(req, st, cache, produced, scores, raw_logits, tm)
+        if feed is not None:
+            feed.finish(res["sequences"] if isinstance(res, dict) else res)
+        return res
 
     def _score(self, req, st, step_idx, scores, raw_logits):
         """The device route's per-step callback: appends HF's `scores` of the step (the processed logits, EOS at -inf while step < min_new_tokens) and the raw logits."""
@@ -718,14 +743,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         """The device route's result: the host mirrors of what the loop advanced, the EOS trim, then the tokens, generate()'s dict or score()'s."""
         cache.full_len_host = [n + produced - 1 for n in cache.full_len_host]  # every row's un-evicted length grows by one per decode step
         cache.seen_tokens += produced - 1
-        out = st.out_ids[:, :produced].clone()
-        if req.eos:  # HF stops as soon as every row has emitted EOS: trim the columns produced after that
-            hit = out == req.eos[0]
-            for e_ in req.eos[1:]:
-                hit = hit | (out == e_)
-            all_done = hit.int().cumsum(dim=1).clamp(max=1).min(dim=0).values
-            if bool(all_done.any().item()):
-                first = int(torch.argmax(all_done).item())
+        out, finish = st.out_ids[:, :produced].clone(), None
+        if req.eos or req.stops:  # HF stops as soon as every row has finished (an EOS id, or a stop sequence's last token): trim the columns produced after that
+            finish = stopping.finish_columns(out, req.eos, req.stops)
+            first = int(finish.max().item())
+            if first < out.shape[1]:
                 out, scores, raw_logits = out[:, : first + 1], scores[: first + 1], raw_logits[: first + 1]
         self.last_cache = cache
         if tm is not None:
@@ -748,7 +770,11 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             res["logits"] = tuple(raw_logits)
         if req.n_lp >= 0:  # the columns `sequences` kept; after a row's first EOS (pad in `sequences`) 0.0 / -1
             W, n = out.shape[1], req.n_lp
-            lp, top_lp, top_ids = logprobs.mask_after_eos(out, req.eos, st.lp[:, :W].clone(), st.top_lp[:, :W, :n].clone(), st.top_ids[:, :W, :n].clone())
+            lp, top_lp, top_ids = st.lp[:, :W].clone(), st.top_lp[:, :W, :n].clone(), st.top_ids[:, :W, :n].clone()
+            if req.stops:  # (a row also finishes on a stop sequence: by its finish column)
+                logprobs.mask_after_columns(finish, lp, top_lp, top_ids)
+            else:
+                logprobs.mask_after_eos(out, req.eos, lp, top_lp, top_ids)
             res["logprobs"] = lp
             if n > 0:
                 res["top_logprobs"], res["top_logprob_ids"] = top_lp, top_ids

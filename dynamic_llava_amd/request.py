@@ -7,20 +7,22 @@ from typing import Any, Optional, Tuple
 
 import torch
 
-from . import logits_rules, logprobs, sampling
+from . import logits_rules, logprobs, sampling, stopping
 from .sampling import eos_ids  # the only resolver of eos_token_id; defined in that leaf module because sampling.device_route needs it too
 
 
 def route(kwargs, rules, vocab_size, default_eos) -> str:
     """Which body of generate() serves the kwargs (the table is in DESIGN.md): "device" (the captured graphs), "host_sample" (_generate_sample), "host_greedy"
     (_generate_sample(greedy=True), without do_sample / sync_every) or "on_cache" (_generate_on_cache).  Past the device caps -- logits_rules.MAX_*, or more EOS
-    ids than the step-closing kernels compare -- a request takes the plain loop over forward(), which applies the same rule on the host."""
+    ids than the step-closing kernels compare, or stopping.MAX_STOPS / MAX_STOP_LEN -- a request takes the plain loop over forward(), which applies the same rule on
+    the host; so does a request with a stopping criterion that is a callable (stopping.host_criteria), which only the host can call."""
     sample = bool(kwargs.get("do_sample", False))
     if sample and not sampling.device_route(kwargs, vocab_size, default_eos):
         return "host_sample"  # (KNOWN DEFECT: with past_key_values too -- _generate_sample never reads them, the dialogue is dropped without a word)
     if kwargs.get("past_key_values") is not None:
         return "on_cache"
-    if (rules.on and not rules.device_route) or len(eos_ids(kwargs, default_eos)) > sampling.MAX_EOS_IDS:
+    past_stop_caps = bool(stopping.host_criteria(kwargs)) or not stopping.device_route(stopping.normalize(kwargs, vocab_size))
+    if (rules.on and not rules.device_route) or len(eos_ids(kwargs, default_eos)) > sampling.MAX_EOS_IDS or past_stop_caps:
         return "host_sample" if sample else "host_greedy"
     return "device"
 
@@ -67,6 +69,14 @@ class Request:
     max_new_tokens: Optional[int]
     max_length: Optional[int]
     n_return: int = 1  # num_return_sequences: sampled answers per prompt, rows b * n .. b * n + n - 1 of every per-row result
+    stops: Tuple[Tuple[int, ...], ...] = ()  # stop_sequences= and the keyword criteria of stopping_criteria= (stopping.normalize): a row finishes when its tokens end in one
+    criteria: tuple = ()  # the other items of stopping_criteria=: callables, served by the host loop only
+    streamer: Any = None  # put(tensor) / end(): receives the tokens as they come (stopping.Feed)
+
+    @property
+    def can_finish(self) -> bool:
+        """Some row may finish before max_new tokens: there is an EOS set, a stop sequence or a host criterion."""
+        return bool(self.eos) or bool(self.stops) or bool(self.criteria)
 
     def max_new(self, lens) -> int:
         """The number of steps: max_new_tokens, or max_length - the longest prompt (HF's default: 20 steps)."""
@@ -80,12 +90,18 @@ class Request:
 
 def parse(kwargs, config, sync_every=None) -> Request:
     """generate()'s **kwargs -> Request.  Every keyword is validated here, before any device work, in this order: the logits processors, score() with
-    processors, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences, the sampling parameters."""
+    processors, the stop sequences and criteria, score() with those, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences, the sampling parameters."""
     V, eos = config.vocab_size, eos_ids(kwargs, config.eos_token_id)
     rules = logits_rules.normalize(kwargs, V, eos)  # (a one-token bad word equal to an EOS id is dropped, as in HF)
     forced = kwargs.get("_score_labels")
     if rules.on and forced is not None:
         raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
+    stops, criteria = stopping.normalize(kwargs, V), stopping.host_criteria(kwargs)
+    if (stops or criteria) and forced is not None:
+        raise ValueError("score() takes neither stop sequences nor stopping criteria: the label sequence ends a row")
+    streamer = kwargs.get("streamer")
+    if streamer is not None and not (callable(getattr(streamer, "put", None)) and callable(getattr(streamer, "end", None))):
+        raise ValueError(f"streamer must have put(tensor) and end() (got {type(streamer).__name__})")
     n_lp = logprobs.validate(kwargs, V)
     if "inputs_embeds" in kwargs:
         raise NotImplementedError("`inputs_embeds` is not supported")  # DLL:128-129
@@ -101,17 +117,26 @@ def parse(kwargs, config, sync_every=None) -> Request:
                    temperature=float(kwargs.get("temperature", 1.0) or 1.0), top_k=int(kwargs.get("top_k", 0) or 0), top_p=None if top_p is None else float(top_p),
                    generator=kwargs.get("generator"), want_dict=want_dict, want_scores=want_dict and bool(kwargs.get("output_scores")), want_logits=want_dict and bool(kwargs.get("output_logits")),
                    sync_every=sync_every if kwargs.get("sync_every") is None else int(kwargs["sync_every"]), forced=forced, attention_mask=kwargs.get("attention_mask"),
-                   image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"), n_return=n_return)
+                   image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"), n_return=n_return,
+                   stops=stops, criteria=criteria, streamer=streamer)
 
 
-def host_loop(logits, advance, req: Request, max_new: int, greedy: bool):
+def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=None):
     """The plain decoding loop of the host routes.  logits: the first step's fp32 [B, V]; advance(next_ids [B]) -> the next step's, called once per token but the
     last.  Per step, in HF's order: the logits processors on the tokens emitted in this call, temperature, the EOS ban of min_new_tokens, top-k, top-p, then the
     argmax (`greedy`) or a draw with torch's generator; pad behind a row's EOS; stops when every row has finished.  -> (tokens: a list of [B], scores: the
-    processed logits per step, raw: the model's own logits per step, kept only when log-probabilities are asked for).  No device work of its own."""
+    processed logits per step, raw: the model's own logits per step, kept only when log-probabilities are asked for).  No device work of its own.
+    req.stops: a row also finishes when its emitted tokens end in a stop sequence (stopping.tail_matches; min_new_tokens does not hold that back).  req.criteria:
+    every callable is called once per step as c(ids [B, t], scores [B, V]) -- the tokens emitted in this call, this step's included, as HF calls a criterion when
+    driven by inputs_embeds, and the step's processed logits -- and returns a bool (every row) or a bool tensor [B].  req.streamer: put(an empty [B, 0] tensor)
+    first, put(tokens [B] on the CPU) after every pick, end() once.  finish: a list that receives one int64 [B] tensor, the column at which each row finished
+    (the number of tokens where it did not)."""
     B, eos = logits.shape[0], list(req.eos)
     finished = torch.zeros(B, dtype=torch.bool, device=logits.device)
+    finish_col = torch.full((B,), max_new, dtype=torch.int64, device=logits.device)
     toks, scores, raw = [], [], []
+    if req.streamer is not None:
+        req.streamer.put(torch.zeros((B, 0), dtype=torch.int64))
     for step in range(max_new):
         z = logits
         if req.n_lp >= 0:
@@ -133,10 +158,26 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool):
         nxt = z.argmax(dim=-1) if greedy else torch.multinomial(z.softmax(dim=-1), 1, generator=req.generator)[:, 0]
         nxt = torch.where(finished, torch.full_like(nxt, req.pad), nxt)
         toks.append(nxt)
+        if req.streamer is not None:
+            req.streamer.put(nxt.detach().to("cpu", torch.int64))
+        was = finished
         for e in eos:
             finished = finished | (nxt == e)
-        if eos and bool(finished.all()):
+        if req.stops or req.criteria:
+            ids = torch.stack(toks, dim=1)
+            if req.stops:
+                finished = finished | torch.tensor([stopping.tail_matches(row, req.stops) for row in ids.tolist()], dtype=torch.bool, device=finished.device)
+            for c in req.criteria:
+                r = c(ids, z)
+                finished = finished | (r.to(device=finished.device, dtype=torch.bool).reshape(B) if torch.is_tensor(r) else torch.full_like(finished, bool(r)))
+        if finish is not None:
+            finish_col = torch.where(finished & ~was, torch.full_like(finish_col, step), finish_col)
+        if req.can_finish and bool(finished.all()):
             break
         if step + 1 < max_new:
             logits = advance(nxt)
+    if finish is not None:
+        finish.append(finish_col.clamp(max=len(toks)))
+    if req.streamer is not None:
+        req.streamer.end()
     return toks, scores, raw

@@ -517,6 +517,26 @@ int dl_decode_logprobs(const void* logits, int logits_dtype, int64_t logits_row_
                        const int64_t* next_ids, const int32_t* step, int cap, float* logprobs,
                        int n_top, int top_stride, float* top_logprobs, int64_t* top_ids, void* stream);
 
+/* ---- stop sequences of a generation (generate(stop_sequences= / stopping_criteria=)): runs AFTER the step-closing launch (dl_decode_advance /
+ * dl_decode_sample; behind dl_decode_logprobs when that runs), which has appended the row's token.  Replaces the token-tail check of the reference's
+ * KeywordsStoppingCriteria (llava/mm_utils.py:257-267: `output_ids[0, -len(keyword):] == keyword` after every step), per row and on the tokens generated
+ * in this call; the criterion's decoded-text search (mm_utils.py:268-274) needs a tokenizer and is not built.
+ * Per row b (dynamic_llava_amd/stopping.py states the rule in full and is what the kernel is tested against): when finished[b] == 0, with
+ * t = min(step[b], out_cap) and g = out_ids[b, 0 : t], finished[b] = 1 if for some i < min(table->n_stops, DL_STOP_MAX_SEQS) the sequence
+ * w = table->seq[i][1 : 1 + len], len = table->seq[i][0] in 1..DL_STOP_MAX_LEN, has len <= t and g[t - len : t] == w.  Nothing else is written: a finished
+ * row is not touched, n_stops <= 0 writes nothing, out_ids and step are only read, and nothing in front of column 0 of a row is read.  Table slots past
+ * n_stops, or past a sequence's length, may hold anything.  table: DEVICE memory (one captured graph serves every stop list; the host rewrites it
+ * between requests).  out_ids: int64 [B, out_cap]; step, finished: int32 [B].  One wave per row; no workspace, no atomics, never synchronises:
+ * capturable.  DL_ERR_ARG, and nothing enqueued, for a NULL pointer, B < 1 or out_cap < 1. */
+#define DL_STOP_MAX_SEQS 8
+#define DL_STOP_MAX_LEN 8
+typedef struct dl_stop_table {
+  int32_t n_stops;
+  int32_t reserved[7];
+  int32_t seq[DL_STOP_MAX_SEQS][1 + DL_STOP_MAX_LEN]; /* a length, then the ids */
+} dl_stop_table;
+int dl_decode_stop(const int64_t* out_ids, int out_cap, int B, const int32_t* step, int32_t* finished, const dl_stop_table* table, void* stream);
+
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
  * operand registers).  bf16 / f16, fp32 accumulate, one rounding.  K % 256 == 0, N % 4 == 0; ldx / ldy: row strides (elements).
