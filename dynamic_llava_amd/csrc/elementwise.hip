@@ -141,7 +141,6 @@ __global__ __launch_bounds__(kThreads) void layernorm_kernel(const void* x_, con
   const int64_t src = row_index ? (int64_t)row_index[row] : row;
   const S* xr = reinterpret_cast<const S*>(x_) + src * H;
   const S* delta = ADD == 1 ? reinterpret_cast<const S*>(delta_) + row * H : nullptr;
-  const float* parts = ADD == 2 ? reinterpret_cast<const float*>(delta_) + row * H : nullptr;
   const int nvec = H / V;
   float x[kMaxVecPerThread][V];
   float s = 0.f;

@@ -2,8 +2,11 @@
 asserts on -- reported instead of asserted.  Per kernel x dtype x distribution: the worst err / tol under the per-element bound of
 oracle/attn_truth.py, and the worst error in ULP of the element itself.
 
-    python tools/attn_error_table.py [--skip-decode] > table.md        (needs the GPU)"""
+    python tools/attn_error_table.py [--skip-decode] > table.md        (needs the GPU)
+    python tools/attn_error_table.py --digest [--library other.so]     SHA-256 of every prefill output of the same tables, one line per launch:
+                                                                       run it on two builds and diff the listings (same bits or not)"""
 import argparse
+import hashlib
 import os
 import sys
 
@@ -33,11 +36,41 @@ def _print(title, acc, dists):
     sys.stdout.flush()
 
 
+def digests():
+    """The prefill launches of the two tables with every output tensor hashed instead of judged (ac.run_prefill / ac.run_cached hand the tensors back)."""
+
+    def one(label, run):
+        outs = []
+        run(outs)
+        print(label, *(hashlib.sha256(o.view(torch.uint8).numpy().tobytes()).hexdigest() for o in outs))
+        sys.stdout.flush()
+
+    for e in ac.PREFILL_TABLE:
+        if e.route == "NONE":
+            continue
+        with ac.pf_env(e.env):
+            for dtype in e.dtypes:
+                assert ac.prefill_route(ops, e, dtype) == e.route, e.id
+                for dist in at.DISTRIBUTIONS:
+                    one(f"prefill {e.id} {DT[dtype]} {dist}", lambda outs: ac.run_prefill(ops, e, dist, dtype, outputs=outs))
+    with ac.pf_env({}):
+        for entry in ac.CACHED_TABLE:
+            for dtype in ((torch.float32,) if entry[0] == "SIMPLE_F32" else (torch.bfloat16, torch.float16)):
+                for dist in at.DISTRIBUTIONS:
+                    one(f"cached {entry[0]}-h{entry[1]}kv{entry[2]}d{entry[3]} {DT[dtype]} {dist}", lambda outs: ac.run_cached(ops, entry, dist, dtype, outputs=outs))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-decode", action="store_true")
+    ap.add_argument("--digest", action="store_true", help="print the SHA-256 of every prefill output instead of the error table")
+    ap.add_argument("--library", help="load this build of the library instead of the tree's")
     args = ap.parse_args()
+    if args.library:
+        ops.load_library(args.library)
     ops.require_gpu()
+    if args.digest:
+        return digests()
     print("Each cell: worst err / tol (worst error in ULP of the element).")
     acc = {}
     for e in ac.PREFILL_TABLE:
