@@ -57,6 +57,10 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
   const int split = blockIdx.x, n_splits = gridDim.x, h = blockIdx.y;
   const int n_heads = gridDim.y;
   const int tid = threadIdx.x;
+  // (The ranking below and the partial store at the end are attn_rank_row's and attn_store_partial's text, which attn_decode_kv8.hip calls.  They stay written out
+  // here: called as functions they leave registers, scratch and occupancy alone but reorder this kernel's prologue and epilogue, and that build's keys_in_flight
+  // 256 form measured 0.3-0.9 % slower than its predecessor in both orders of an alternation -- the last section of profiles/attn_decode_refactor_timing.txt.
+  // Written out, every instantiation of this kernel compiles to the instruction stream it had before the stages were shared.)
   // Ragged batches, longest row first (round 6): workgroups are dispatched in blockIdx order (x, then y, then z), so slice z of the grid takes the row with
   // the z-th LARGEST length (ties: lower row index) instead of row z -- the long rows start first and the short ones fill the tail, whatever order the caller's
   // batch is in (a batch of 32 requests with 200..900 keys otherwise ends with a few CUs finishing their 900-key rows alone).  Every wave ranks the <= 64
@@ -154,8 +158,6 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_split_kernel(
   DL_STAMP(4, true);  // stores acknowledged
   }
 }
-
-// (kMaxSplits and attn_decode_combine_kernel, the merge of the split partials, live in attn_decode_body.h: attn_decode_kv8.hip launches the same kernel)
 
 // workgroups of `kfn` (block threads, dynamic LDS bytes) the current device holds at once, at most 4 per CU (the regime the spin-wait of the
 // in-kernel combine was validated in); 0 when the device cannot be queried.  Cached per (kernel, device).

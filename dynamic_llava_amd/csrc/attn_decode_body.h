@@ -1,14 +1,20 @@
 // Body of the split-KV decode attention (F9 decode + F11: RoPE of q / new key, KV-slab append, ragged attention over an evicted
-// slab), shared by the stand-alone launch (attn_decode.hip: one 256-thread workgroup per (split, head, row)) and by the attention workgroups
-// of the fused batch-1 q|k|v launch (gemv.hip, dl_gemv_qkv_attn: 1..4 workgroups per head fed their q / k / v rows as granules).  Sharing the
-// code keeps the two paths in one arithmetic: same key -> lane-group dealing, same online-softmax batching, same merge orders (the fused
-// launch folds the new token in after the slab merge -- attn_split_finish_newlast -- so its output is in the same rounding class, not the
-// same bits; projection row, residual stream and appended K/V are bit-identical).
+// slab), shared by three callers:
+//   attn_decode.hip      the stand-alone launch: one 256-thread workgroup per (split, head, row)
+//   gemv.hip             the attention workgroups of the fused batch-1 q|k|v launch (dl_gemv_qkv_attn: 1..4 workgroups per head fed their q / k / v rows as granules)
+//   attn_decode_kv8.hip  the stand-alone launch over the MXFP8 KV cache's planes
+// Sharing the code keeps the paths in one arithmetic: same row ranking, same split ranges, same key -> lane-group dealing, same online-softmax batching,
+// same merge orders.  What differs between them is (a) how a slab row is stored -- a row-format policy (KvModelRows below, KvMx8Rows in attn_decode_kv8.hip)
+// that owns the request, the unpacking and the two arithmetic expressions that touch a row -- and (b) when the new token joins the softmax: last in its lane
+// group (attn_split_finish), after the slab merge (attn_split_finish_newlast, the fused launch), or first in its lane group (attn_decode_kv8.hip).  The three
+// orders give the same value up to fp32 rounding, not the same bits; projection row, residual stream and appended K/V are bit-identical.
 //
-// Two parts, so that a caller can have the K/V rows in flight before the query exists:
-//   attn_split_issue  -- needs only kv_len / the slab: key range of the split, first K/V rows requested
-//   attn_split_finish -- needs the q (and, for the split that owns the new token, k / v) rows: RoPE, scores, online softmax,
-//                        P.V, the appended token, merge of the workgroup's lane groups -> (M, L, O[d]) for thread d < D
+// Stages, so that a caller can have the K/V rows in flight before the query exists:
+//   attn_rank_row        -- which row of a ragged batch this grid slice takes
+//   attn_split_issue     -- needs only kv_len / the slab: key range of the split, first K/V rows requested
+//   attn_split_keys      -- needs q: scores, online softmax and P.V over the split's slab keys, one trip requested ahead
+//   attn_split_lds_merge -- the workgroup's lane groups -> (M, L, O[d]) for thread d < D;  attn_store_partial: output or workspace partial
+//   attn_split_finish    -- the model-dtype kernels' sequence around them: RoPE of q / the new key, keys, the appended token, merge
 #pragma once
 #include "dl_common.h"
 
@@ -40,18 +46,22 @@ __global__ __launch_bounds__(D) void attn_decode_combine_kernel(const float* __r
   store1<T>(out_, (int64_t)b * out_row_stride + (int64_t)h * D + d, o[0]);
 }
 
-template <typename T, bool UPPER>
-__device__ __forceinline__ void rope16(const float (&own)[Elem<T>::kVec], const float (&par)[Elem<T>::kVec], const float (&cs)[Elem<T>::kVec],
-                                       const float (&sn)[Elem<T>::kVec], float (&out)[Elem<T>::kVec]) {
+// `upper`: this lane's columns are the upper half.  The model-dtype kernels branch on it and pass a constant (their code as it always was); the MXFP8 kernel
+// passes the lane's value and gets a select (branching there costs it 5 to 13 VGPRs, up to the last one that keeps 3 waves per SIMD).
+template <typename T, int E>
+__device__ __forceinline__ void rope16(bool upper, const float (&own)[E], const float (&par)[E], const float (&cs)[E], const float (&sn)[E], float (&out)[E]) {
 #pragma unroll
-  for (int i = 0; i < Elem<T>::kVec; ++i)  // x*cos + rotate_half(x)*sin, each op rounded (DML:283-284); rotate_half = cat(-x2, x1)
-    out[i] = Elem<T>::round(Elem<T>::round(own[i] * cs[i]) + Elem<T>::round((UPPER ? par[i] : -par[i]) * sn[i]));
+  for (int i = 0; i < E; ++i)  // x*cos + rotate_half(x)*sin, each op rounded (DML:283-284); rotate_half = cat(-x2, x1)
+    out[i] = Elem<T>::round(Elem<T>::round(own[i] * cs[i]) + Elem<T>::round((upper ? par[i] : -par[i]) * sn[i]));
 }
 
-// sum over the LPK lanes that share one key (8, 16 or 32 lanes, aligned): DPP inside a 16-lane row, one crossbar step beyond it
+// sum over the LPK lanes that share one key (4, 8, 16 or 32 lanes, aligned): DPP inside a 16-lane row, one crossbar step beyond it
 template <int LPK>
 __device__ __forceinline__ float lpk_sum(float a) {
-  if constexpr (LPK == 8) return row8_sum(a);
+  if constexpr (LPK == 4) {
+    a += dpp_f32<kDppXor1>(a);
+    return a + dpp_f32<kDppXor2>(a);
+  } else if constexpr (LPK == 8) return row8_sum(a);
   else if constexpr (LPK == 16) return row16_sum(a);
   else if constexpr (LPK == 32) {
     a = row16_sum(a);
@@ -87,45 +97,81 @@ __device__ __forceinline__ void unpack_kv(const uint4& r, float (&f)[Elem<T>::kV
   }
 }
 
-// Geometry of one split: D/kVec lanes cooperate on one key (16 lanes x 16 B = one 256-byte K row for D=128 bf16), so a wave-wide load
+// ---- how a K/V row of the slab is stored: the policy F of the stages below ----
+//   E, kMergeRegsNG            elements of a row one lane holds (LPK = D / E lanes share a key); see attn_split_lds_merge
+//   Slab / Ptr / Raw           what the caller hands over for K or for V; the same advanced to (row, kv head, this lane's columns); the registers of one requested row
+//   at, request                Ptr of a lane; one key's K and V rows requested together
+//   unpack, dot, axpy          Raw -> E floats; this lane's share of q.k (before the lane-group sum); o += p * v with a masked slot SELECTED away (never
+//                              multiplied by zero: a speculatively read slot past the length may hold NaN bits).  Written out per format, exactly as its kernel
+//                              always had them -- the explicit fmaf and the select form are part of the result's bits.
+// KvModelRows (here): rows of the model dtype, 16 bytes per lane.  KvMx8Rows (attn_decode_kv8.hip): e4m3 codes + one E8M0 scale byte per 32 elements, in planes.
+template <typename T>
+struct KvModelRows {
+  static constexpr int E = Elem<T>::kVec;
+  static constexpr int kMergeRegsNG = 64;  // attn_split_lds_merge: up to this many lane groups' partials are read into registers up front (here: always)
+  using Slab = const void*;
+  using Ptr = const typename Elem<T>::storage*;
+  using Raw = uint4;
+  static __device__ __forceinline__ Ptr at(Slab slab, int64_t stride_b, int64_t stride_h, int b, int kvh, int c) {
+    return reinterpret_cast<Ptr>(slab) + (int64_t)b * stride_b + (int64_t)kvh * stride_h + c;
+  }
+  static __device__ __forceinline__ void request(Ptr kb, Ptr vb, int64_t key, int D, Raw& k, Raw& v) {
+    k = kv_ld16(kb + key * D);
+    v = kv_ld16(vb + key * D);
+  }
+  static __device__ __forceinline__ void unpack(const Raw& r, float (&f)[E]) { unpack_kv<T>(r, f); }
+  static __device__ __forceinline__ float dot(const float (&q)[E], const float (&kx)[E], const Raw&) {
+    float a = 0.f;
+#pragma unroll
+    for (int i = 0; i < E; ++i) a += q[i] * kx[i];
+    return a;
+  }
+  static __device__ __forceinline__ void axpy(bool ok, float p, const float (&vx)[E], const Raw&, float (&o)[E]) {
+#pragma unroll
+    for (int i = 0; i < E; ++i) o[i] += ok ? p * vx[i] : 0.f;
+  }
+};
+
+// Geometry of one split: LPK = D/E lanes cooperate on one key (16 lanes x 16 B = one 256-byte K row for D=128 bf16), so a wave-wide load
 // is KPW full rows; NW waves = NG lane groups; U key rows per lane group are requested per loop trip.
-template <typename T, int D, int NW, int U>
+template <typename T, int D, int NW, int U, typename F = KvModelRows<T>>
 struct AttnSplitState {
-  static constexpr int V = Elem<T>::kVec;
-  static constexpr int LPK = D / V;
+  static constexpr int E = F::E;
+  static constexpr int LPK = D / E;
   static constexpr int KPW = 64 / LPK;
   static constexpr int NG = NW * KPW;
   using S = typename Elem<T>::storage;
-  const S* kb;
-  const S* vb;
+  using Raw = typename F::Raw;
+  typename F::Ptr kb, vb;
   int T_old, Tn, chunk, k0, k1s, k1;
   int wid, lane, g, c;  // wave inside the (virtual) workgroup, lane, lane group inside the wave, first head dim of this lane
   bool spec;
   bool ok[U];
-  uint4 kraw[U], vraw[U];
+  Raw kraw[U], vraw[U];
   // second trip, requested ahead of the first one's consumption (attn_split_prefetch2: callers that have to wait for q anyway)
   bool pre2;
   bool ok2[U <= 4 ? U : 1];
-  uint4 kraw2[U <= 4 ? U : 1], vraw2[U <= 4 ? U : 1];
+  Raw kraw2[U <= 4 ? U : 1], vraw2[U <= 4 ? U : 1];
+  // keys of this workgroup are dealt round-robin over its lane groups
+  __device__ __forceinline__ int key(int base, int u) const { return base + (u * NW + wid) * KPW + g; }
 };
 
 // Part 1.  `vtid`: thread index inside the (virtual) workgroup of NW waves.  Every load that does not depend on another load is
 // issued here, K/V first: a dependent HBM round trip costs ~1.5 us, so the latency is (number of round trips), not bytes.  With a
 // host-provided chunk (chunk_keys > 0, needs T_cap) the key range does not depend on kv_len either: the rows are requested
 // speculatively (any slot < T_cap is readable) and masked once kv_len[b] has arrived.
-template <typename T, int D, int NW, bool FUSED, int U>
-__device__ __forceinline__ void attn_split_issue(AttnSplitState<T, D, NW, U>& s, int vtid, const void* k_slab_, const void* v_slab_,
+template <typename T, int D, int NW, bool FUSED, int U, typename F>
+__device__ __forceinline__ void attn_split_issue(AttnSplitState<T, D, NW, U, F>& s, int vtid, const typename F::Slab& k_slab, const typename F::Slab& v_slab,
                                                  int64_t stride_b, int64_t stride_h, int T_old, int extra, int b, int kvh, int split,
                                                  int n_splits, int T_cap, int chunk_keys) {
-  using St = AttnSplitState<T, D, NW, U>;
-  using S = typename St::S;
-  constexpr int V = St::V, LPK = St::LPK, KPW = St::KPW, NG = St::NG;
+  using St = AttnSplitState<T, D, NW, U, F>;
+  constexpr int LPK = St::LPK, NG = St::NG;
   s.lane = vtid & 63;
   s.wid = vtid >> 6;
   s.g = s.lane / LPK;
-  s.c = (s.lane % LPK) * V;
-  s.kb = reinterpret_cast<const S*>(k_slab_) + (int64_t)b * stride_b + (int64_t)kvh * stride_h + s.c;
-  s.vb = reinterpret_cast<const S*>(v_slab_) + (int64_t)b * stride_b + (int64_t)kvh * stride_h + s.c;
+  s.c = (s.lane % LPK) * F::E;
+  s.kb = F::at(k_slab, stride_b, stride_h, b, kvh, s.c);
+  s.vb = F::at(v_slab, stride_b, stride_h, b, kvh, s.c);
   s.T_old = T_old;
   s.pre2 = false;
   s.spec = chunk_keys > 0 && T_cap > 0;
@@ -135,11 +181,7 @@ __device__ __forceinline__ void attn_split_issue(AttnSplitState<T, D, NW, U>& s,
     s.chunk = (chunk_keys + NG - 1) / NG * NG;
     s.k0 = split * s.chunk;
 #pragma unroll
-    for (int u = 0; u < U; ++u) {
-      const int key = min(s.k0 + (u * NW + s.wid) * KPW + s.g, T_cap - 1);
-      s.kraw[u] = kv_ld16(s.kb + (int64_t)key * D);
-      s.vraw[u] = kv_ld16(s.vb + (int64_t)key * D);
-    }
+    for (int u = 0; u < U; ++u) F::request(s.kb, s.vb, (int64_t)min(s.key(s.k0, u), T_cap - 1), D, s.kraw[u], s.vraw[u]);
   }
   s.Tn = T_old + (FUSED ? 1 : extra);
   if (!s.spec) {
@@ -152,56 +194,50 @@ __device__ __forceinline__ void attn_split_issue(AttnSplitState<T, D, NW, U>& s,
   s.k1 = FUSED ? min(s.k1s, T_old) : s.k1s;  // ... of which [k0, k1) are read from the slab
 #pragma unroll
   for (int u = 0; u < U; ++u) {
-    const int key = s.k0 + (u * NW + s.wid) * KPW + s.g;
+    const int key = s.key(s.k0, u);
     s.ok[u] = key < s.k1;
-    if (!s.spec) {
-      const int64_t off = (int64_t)(s.ok[u] ? key : (s.k0 < s.k1 ? s.k0 : 0)) * D;
-      s.kraw[u] = kv_ld16(s.kb + off);
-      s.vraw[u] = kv_ld16(s.vb + off);
-    }
+    if (!s.spec) F::request(s.kb, s.vb, (int64_t)(s.ok[u] ? key : (s.k0 < s.k1 ? s.k0 : 0)), D, s.kraw[u], s.vraw[u]);
   }
 }
 
-// Optional, between the two parts: request the SECOND trip's rows too (U <= 4).  attn_split_finish requests trip i + 1 when it starts on trip i;
+// Optional, between the two parts: request the SECOND trip's rows too (U <= 4).  attn_split_keys requests trip i + 1 when it starts on trip i;
 // a caller that cannot start yet (dl_gemv_qkv_attn waits for q) puts two trips in flight meanwhile.  Loads only: results unchanged.
-template <typename T, int D, int NW, int U>
-__device__ __forceinline__ void attn_split_prefetch2(AttnSplitState<T, D, NW, U>& s) {
-  using St = AttnSplitState<T, D, NW, U>;
-  constexpr int KPW = St::KPW, NG = St::NG;
+template <typename T, int D, int NW, int U, typename F>
+__device__ __forceinline__ void attn_split_prefetch2(AttnSplitState<T, D, NW, U, F>& s) {
+  constexpr int NG = AttnSplitState<T, D, NW, U, F>::NG;
   if constexpr (U <= 4) {
-    const int nbase = s.k0 + NG * U;
-    if (nbase < s.k1) {
+    if (s.k0 + NG * U < s.k1) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int key = nbase + (u * NW + s.wid) * KPW + s.g;
+        const int key = s.key(s.k0 + NG * U, u);
         s.ok2[u] = key < s.k1;
-        const int64_t off = (int64_t)(s.ok2[u] ? key : s.k0) * D;
-        s.kraw2[u] = kv_ld16(s.kb + off);
-        s.vraw2[u] = kv_ld16(s.vb + off);
+        F::request(s.kb, s.vb, (int64_t)(s.ok2[u] ? key : s.k0), D, s.kraw2[u], s.vraw2[u]);
       }
       s.pre2 = true;
     }
   }
 }
 
-// ---- the two halves of attn_split_finish that the "new key last" variant below shares with it (same code, same order, same bits) ----
-// Online softmax over this split's slab keys [k0, k1): per lane group (m, l, o[V]).
-template <typename T, int D, int NW, int U>
-__device__ __forceinline__ void attn_split_keys(AttnSplitState<T, D, NW, U>& s, const float (&qv)[Elem<T>::kVec], float scale, float& m, float& l,
-                                                float (&o)[Elem<T>::kVec]) {
-  using St = AttnSplitState<T, D, NW, U>;
-  constexpr int V = St::V, LPK = St::LPK, KPW = St::KPW, NG = St::NG;
-  const int g = s.g, wid = s.wid;
+// An empty online-softmax state
+template <int E>
+__device__ __forceinline__ void attn_softmax_open(float& m, float& l, float (&o)[E]) {
   m = -INFINITY;
   l = 0.f;
 #pragma unroll
-  for (int i = 0; i < V; ++i) o[i] = 0.f;
+  for (int i = 0; i < E; ++i) o[i] = 0.f;
+}
 
-  // keys of this workgroup are dealt round-robin: key = base + (u * NW + wid) * KPW + g
+// ---- the stages every finish sequence shares (same code, same order, same bits) ----
+// Online softmax over this split's slab keys [k0, k1), continued on the lane group's state (m, l, o[E]) -- opened by the caller: empty
+// (attn_softmax_open), or holding the new token already (attn_decode_kv8.hip).
+template <typename T, int D, int NW, int U, typename F>
+__device__ __forceinline__ void attn_split_keys(AttnSplitState<T, D, NW, U, F>& s, const float (&qv)[F::E], float scale, float& m, float& l, float (&o)[F::E]) {
+  using St = AttnSplitState<T, D, NW, U, F>;
+  constexpr int E = St::E, LPK = St::LPK, NG = St::NG;
   // the rows of trip i + 1 are requested before trip i is consumed (U <= 4: the registers are there): a row of T keys is a chain of
   // T / (NG U) trips, and without this every trip paid a full memory round trip (the longest row of a ragged batch sets the launch time)
   constexpr bool kPrefetch = U <= 4;
-  uint4 kpre[kPrefetch ? U : 1], vpre[kPrefetch ? U : 1];
+  typename F::Raw kpre[kPrefetch ? U : 1], vpre[kPrefetch ? U : 1];
   bool okpre[kPrefetch ? U : 1];
   for (int base = s.k0; base < s.k1; base += NG * U) {
     if constexpr (kPrefetch) {
@@ -217,34 +253,27 @@ __device__ __forceinline__ void attn_split_keys(AttnSplitState<T, D, NW, U>& s, 
         } else {
 #pragma unroll
           for (int u = 0; u < U; ++u) {
-            const int key = nbase + (u * NW + wid) * KPW + g;
+            const int key = s.key(nbase, u);
             okpre[u] = key < s.k1;
-            const int64_t off = (int64_t)(okpre[u] ? key : s.k0) * D;
-            kpre[u] = kv_ld16(s.kb + off);
-            vpre[u] = kv_ld16(s.vb + off);
+            F::request(s.kb, s.vb, (int64_t)(okpre[u] ? key : s.k0), D, kpre[u], vpre[u]);
           }
         }
       }
     } else if (base != s.k0) {
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        const int key = base + (u * NW + wid) * KPW + g;
+        const int key = s.key(base, u);
         s.ok[u] = key < s.k1;
-        const int64_t off = (int64_t)(s.ok[u] ? key : s.k0) * D;
-        s.kraw[u] = kv_ld16(s.kb + off);
-        s.vraw[u] = kv_ld16(s.vb + off);
+        F::request(s.kb, s.vb, (int64_t)(s.ok[u] ? key : s.k0), D, s.kraw[u], s.vraw[u]);
       }
     }
     float sc[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
-      float kx[V];
-      unpack_kv<T>(s.kraw[u], kx);
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < V; ++i) a += qv[i] * kx[i];
-      a = lpk_sum<LPK>(a);
-      sc[u] = s.ok[u] ? a * scale : -INFINITY;
+      float kx[E];
+      F::unpack(s.kraw[u], kx);
+      const float a = lpk_sum<LPK>(F::dot(qv, kx, s.kraw[u]));
+      sc[u] = s.ok[u] ? a * scale : -INFINITY;  // a select: a masked slot may have produced NaN / Inf
     }
     float mn = m;
 #pragma unroll
@@ -253,15 +282,14 @@ __device__ __forceinline__ void attn_split_keys(AttnSplitState<T, D, NW, U>& s, 
       const float alpha = __expf(m - mn);  // m = -inf -> 0
       l *= alpha;
 #pragma unroll
-      for (int i = 0; i < V; ++i) o[i] *= alpha;
+      for (int i = 0; i < E; ++i) o[i] *= alpha;
 #pragma unroll
       for (int u = 0; u < U; ++u) {
-        float vx[V];
-        unpack_kv<T>(s.vraw[u], vx);
+        float vx[E];
+        F::unpack(s.vraw[u], vx);
         const float p = __expf(sc[u] - mn);  // masked key: exp(-inf) = 0
         l += p;
-#pragma unroll
-        for (int i = 0; i < V; ++i) o[i] += s.ok[u] ? p * vx[i] : 0.f;  // a speculatively read slot past the length may hold NaN bits
+        F::axpy(s.ok[u], p, vx, s.vraw[u], o);
       }
       m = mn;
     }
@@ -279,47 +307,95 @@ __device__ __forceinline__ void attn_split_keys(AttnSplitState<T, D, NW, U>& s, 
 }
 
 // Merge of the NG lane groups' (m, l, o) through LDS -> (M, L, O) for threads vtid < D.  Contains ONE __syncthreads().
-template <typename T, int D, int NW, int U>
-__device__ __forceinline__ void attn_split_lds_merge(const AttnSplitState<T, D, NW, U>& s, int vtid, float m, float l, const float (&o)[Elem<T>::kVec], float* sm_m,
+template <typename T, int D, int NW, int U, typename F>
+__device__ __forceinline__ void attn_split_lds_merge(const AttnSplitState<T, D, NW, U, F>& s, int vtid, float m, float l, const float (&o)[F::E], float* sm_m,
                                                      float* sm_l, float* sm_o, float& M_out, float& L_out, float& O_out) {
-  using St = AttnSplitState<T, D, NW, U>;
-  constexpr int V = St::V, LPK = St::LPK, KPW = St::KPW, NG = St::NG;
-  const int c = s.c, g = s.g, wid = s.wid, lane = s.lane;
+  using St = AttnSplitState<T, D, NW, U, F>;
+  constexpr int E = St::E, LPK = St::LPK, KPW = St::KPW, NG = St::NG;
+  const int c = s.c, g = s.g, wid = s.wid, lane = s.lane;  // (copies on purpose: with s.c read inside the store loop, dl_gemv_qkv_attn<f32, 64> spilled one dword more)
   const int gg = wid * KPW + g;
   if ((lane % LPK) == 0) {
     sm_m[gg] = m;
     sm_l[gg] = l;
   }
 #pragma unroll
-  for (int i = 0; i < V; ++i) sm_o[gg * D + c + i] = o[i];
+  for (int i = 0; i < E; ++i) sm_o[gg * D + c + i] = o[i];
   __syncthreads();
   M_out = -INFINITY;
   L_out = 0.f;
   O_out = 0.f;
   if (vtid < D) {
-    // NG <= 32 partials: every LDS read is issued before the first use (a rolled loop pays the LDS latency NG times over)
-    float mg[NG], lg[NG], og[NG];
-#pragma unroll
-    for (int i = 0; i < NG; ++i) {
-      mg[i] = sm_m[i];
-      lg[i] = sm_l[i];
-      og[i] = sm_o[i * D + vtid];
-    }
-    float M = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < NG; ++i) M = fmaxf(M, mg[i]);
-    float L = 0.f, O = 0.f;
-    if (M > -INFINITY) {
+    // Every LDS read is issued before the first use (a rolled loop pays the LDS latency NG times over: 2.5 us per launch, +25 % at batch 1, when the eight-wave
+    // head_dim 64 forms with their 64 lane groups were tried that way).  Where the format's kernel has not the registers for 3 NG values (F::kMergeRegsNG): read
+    // where used, eight at a time.  Either way i ascends: the M pass, then L and O.
+    constexpr bool kRegs = NG <= F::kMergeRegsNG;
+    constexpr int kUnroll = kRegs ? NG : 8;
+    float mg[kRegs ? NG : 1], lg[kRegs ? NG : 1], og[kRegs ? NG : 1];
+    if constexpr (kRegs) {
 #pragma unroll
       for (int i = 0; i < NG; ++i) {
-        const float w = __expf(mg[i] - M);  // empty group: exp(-inf) = 0
-        L += lg[i] * w;
-        O += og[i] * w;
+        mg[i] = sm_m[i];
+        lg[i] = sm_l[i];
+        og[i] = sm_o[i * D + vtid];
+      }
+    }
+    auto pick = [](const float* regs, const float* lds, int i, int at) { return kRegs ? regs[i] : lds[at]; };
+    float M = -INFINITY;
+#pragma unroll kUnroll
+    for (int i = 0; i < NG; ++i) M = fmaxf(M, pick(mg, sm_m, i, i));
+    float L = 0.f, O = 0.f;
+    if (M > -INFINITY) {
+#pragma unroll kUnroll
+      for (int i = 0; i < NG; ++i) {
+        const float w = __expf(pick(mg, sm_m, i, i) - M);  // empty group: exp(-inf) = 0
+        L += pick(lg, sm_l, i, i) * w;
+        O += pick(og, sm_o, i, i * D + vtid) * w;
       }
     }
     M_out = M;
     L_out = L;
     O_out = O;
+  }
+}
+
+// What a split leaves behind, by the threads vtid < D: the normalised output when it is the only split, else its partial (M, L, O[D]) in the workspace
+// layout that attn_split_merge reads.  (This and attn_rank_row below: called by attn_decode_kv8.hip; attn_decode_split_kernel keeps the same text written out,
+// see the note there.)
+template <typename T, int D>
+__device__ __forceinline__ void attn_store_partial(int d, int b, int h, int n_heads, int split, int n_splits, float M, float L, float O, float* __restrict__ ws,
+                                                   void* __restrict__ out_, int64_t out_row_stride) {
+  if (n_splits == 1) {
+    store1<T>(out_, (int64_t)b * out_row_stride + (int64_t)h * D + d, L > 0.f ? O / L : 0.f);
+  } else {
+    float* p = ws + (((int64_t)b * n_heads + h) * n_splits + split) * (D + kAttnPartPad);
+    p[kAttnPartPad + d] = O;
+    if (d == 0) {
+      p[0] = M;
+      p[1] = L;
+    }
+  }
+}
+
+// Ragged batches, longest row first (round 6): workgroups are dispatched in blockIdx order (x, then y, then z), so slice z of the grid takes the row with
+// the z-th LARGEST length (ties: lower row index) instead of row z -- the long rows start first and the short ones fill the tail, whatever order the caller's
+// batch is in (a batch of 32 requests with 200..900 keys otherwise ends with a few CUs finishing their 900-key rows alone).  Every wave ranks the <= 64
+// lengths itself (B readlanes); which slice computes a row does not change a bit of the result.
+// T_ranked: the chosen row's length when the ranking has it in a register already (saves the dependent kv_len[b] load: one memory round trip in front of the
+// first K/V request of every workgroup), else -1.
+__device__ __forceinline__ void attn_rank_row(const int32_t* __restrict__ kv_len, int& b, int& T_ranked) {
+  b = blockIdx.z;
+  T_ranked = -1;
+  if (gridDim.z > 1 && gridDim.z <= 64) {
+    const int lane = threadIdx.x & 63, Bn = (int)gridDim.z;
+    const int my = lane < Bn ? kv_len[lane] : -1;
+    int rank = 0;
+    for (int j = 0; j < Bn; ++j) {
+      const int lj = __builtin_amdgcn_readlane(my, j);
+      rank += (lj > my || (lj == my && j < lane)) ? 1 : 0;
+    }
+    const unsigned long long m = __ballot(lane < Bn && rank == (int)blockIdx.z);
+    b = __builtin_amdgcn_readfirstlane(__builtin_ctzll(m));
+    T_ranked = __builtin_amdgcn_readlane(my, b);
   }
 }
 
@@ -369,9 +445,9 @@ __device__ __forceinline__ void attn_split_finish(AttnSplitState<T, D, NW, U>& s
   constexpr bool LATE = !__is_same(BeforeNew, AttnNoWait);
   using St = AttnSplitState<T, D, NW, U>;
   using S = typename St::S;
-  constexpr int V = St::V, LPK = St::LPK, KPW = St::KPW, NG = St::NG;
+  constexpr int V = St::E, LPK = St::LPK;
   constexpr int HALF = D / 2;
-  const int c = s.c, g = s.g, wid = s.wid, lane = s.lane;
+  const int c = s.c, g = s.g, wid = s.wid;
   const int cpar = c < HALF ? c + HALF : c - HALF;
   float qv[V], cs[V], sn[V];
   const bool owns_new = FUSED && s.T_old >= s.k0 && s.T_old < s.k1s && wid == 0 && g == 0;
@@ -396,16 +472,17 @@ __device__ __forceinline__ void attn_split_finish(AttnSplitState<T, D, NW, U>& s
 #pragma unroll
       for (int i = 0; i < V; ++i) kpar[i] = __shfl_xor(owns_new ? kown[i] : 0.f, LPK / 2);
     }
-    if (c < HALF) rope16<T, false>(own, par, cs, sn, qv); else rope16<T, true>(own, par, cs, sn, qv);
+    if (c < HALF) rope16<T>(false, own, par, cs, sn, qv); else rope16<T>(true, own, par, cs, sn, qv);
     if (owns_new && !LATE) {
-      if (c < HALF) rope16<T, false>(kown, kpar, cs, sn, kn); else rope16<T, true>(kown, kpar, cs, sn, kn);
+      if (c < HALF) rope16<T>(false, kown, kpar, cs, sn, kn); else rope16<T>(true, kown, kpar, cs, sn, kn);
     }
   } else {
     load16<T>(reinterpret_cast<const S*>(qrow_) + c, qv);
   }
 
   float m, l, o[V];
-  attn_split_keys<T, D, NW, U>(s, qv, scale, m, l, o);
+  attn_softmax_open(m, l, o);
+  attn_split_keys(s, qv, scale, m, l, o);
 
   if constexpr (FUSED && LATE) {
     before_new();
@@ -414,7 +491,7 @@ __device__ __forceinline__ void attn_split_finish(AttnSplitState<T, D, NW, U>& s
       load16_row<T, NP>(krow_, c, part_stride, kown);
       load16_row<T, NP>(krow_, cpar, part_stride, kpar);
       load16_row<T, NP>(vrow_, c, part_stride, vn);
-      if (c < HALF) rope16<T, false>(kown, kpar, cs, sn, kn); else rope16<T, true>(kown, kpar, cs, sn, kn);
+      if (c < HALF) rope16<T>(false, kown, kpar, cs, sn, kn); else rope16<T>(true, kown, kpar, cs, sn, kn);
     }
   }
   if constexpr (FUSED) {
@@ -442,7 +519,7 @@ __device__ __forceinline__ void attn_split_finish(AttnSplitState<T, D, NW, U>& s
   }
 
   // merge the NG lane groups of this (virtual) workgroup
-  attn_split_lds_merge<T, D, NW, U>(s, vtid, m, l, o, sm_m, sm_l, sm_o, M_out, L_out, O_out);
+  attn_split_lds_merge(s, vtid, m, l, o, sm_m, sm_l, sm_o, M_out, L_out, O_out);
 }
 
 // "New key last" (round 4, dl_gemv_qkv_attn only): the caller's k / v rows are the LAST outputs of the projection that runs in the same launch, so
@@ -507,7 +584,7 @@ __device__ __forceinline__ void attn_split_finish_newlast(AttnSplitState<T, D, N
                                                           float* sm_o, float* red, float& out, FetchKV fetch_kv, AfterSlab after_slab = AfterSlab()) {
   using St = AttnSplitState<T, D, NW, U>;
   using S = typename St::S;
-  constexpr int V = St::V;
+  constexpr int V = St::E;
   constexpr int HALF = D / 2;
   static_assert(D % 64 == 0 && D / 64 <= NW, "the D finishing threads are whole waves of this workgroup");
   const int c = s.c;
@@ -524,10 +601,11 @@ __device__ __forceinline__ void attn_split_finish_newlast(AttnSplitState<T, D, N
   load16<T>(q_rot_lds + c, qv);
   DL_QSTAMP(4);  // q rotated
   float m, l, o[V];
-  attn_split_keys<T, D, NW, U>(s, qv, scale, m, l, o);
+  attn_softmax_open(m, l, o);
+  attn_split_keys(s, qv, scale, m, l, o);
   DL_QSTAMP(5);  // slab keys done (this wave)
   float M, L, O;
-  attn_split_lds_merge<T, D, NW, U>(s, vtid, m, l, o, sm_m, sm_l, sm_o, M, L, O);
+  attn_split_lds_merge(s, vtid, m, l, o, sm_m, sm_l, sm_o, M, L, O);
   DL_QSTAMP(2);  // slab keys merged
   out = 0.f;
   if (!after_slab(M, L, O)) return;

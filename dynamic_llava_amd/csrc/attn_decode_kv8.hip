@@ -42,7 +42,8 @@ __device__ __forceinline__ void kv8_unpack(const uint4& r, float (&f)[kKv8E]) {
   }
 }
 
-// 16 consecutive model-dtype elements
+// 16 consecutive model-dtype elements: the q / k / v / RoPE-table slice of a lane that holds 16 codes (load16 reads one 16-byte vector, 8 or 4 elements: the
+// model-dtype kernels' lane width, so attn_decode_body.h has no wider load to share)
 template <typename T>
 __device__ __forceinline__ void kv8_load_row(const typename Elem<T>::storage* p, float (&f)[kKv8E]) {
   constexpr int V = Elem<T>::kVec;
@@ -55,23 +56,42 @@ __device__ __forceinline__ void kv8_load_row(const typename Elem<T>::storage* p,
   }
 }
 
-// x*cos + rotate_half(x)*sin, each op rounded (DML:283-284; rope16's expression); rotate_half = cat(-x2, x1)
-template <typename T>
-__device__ __forceinline__ void kv8_rope(bool upper, const float (&own)[kKv8E], const float (&par)[kKv8E], const float (&cs)[kKv8E], const float (&sn)[kKv8E],
-                                         float (&out)[kKv8E]) {
+// The row format of the planes, for the stages of attn_decode_body.h (the policy described there).  stride_b / stride_h are the code planes' (bytes =
+// elements); the scale planes' are 1/32 of them.  The scale byte of the lane's block is requested with the codes, never after them.
+struct KvMx8Rows {
+  static constexpr int E = kKv8E;
+  static constexpr int kMergeRegsNG = 32;  // 64 lane groups' partials in registers take the kernel from 150 to 166 VGPRs, of the 168 that keep 3 waves per SIMD
+  struct Slab {
+    uint8_t* codes;  // writable: the kernel appends the new token's row through the same lane pointers
+    uint8_t* scales;
+  };
+  using Ptr = Slab;
+  struct Raw {
+    uint4 q;     // 16 codes
+    uint32_t e;  // the scale byte of their block
+  };
+  static __device__ __forceinline__ Ptr at(const Slab& s, int64_t stride_b, int64_t stride_h, int b, int kvh, int c) {
+    return Ptr{s.codes + (int64_t)b * stride_b + (int64_t)kvh * stride_h + c, s.scales + (int64_t)b * (stride_b >> 5) + (int64_t)kvh * (stride_h >> 5) + (c >> 5)};
+  }
+  static __device__ __forceinline__ void request(const Ptr& kb, const Ptr& vb, int64_t key, int D, Raw& k, Raw& v) {
+    k.q = kv_ld16(kb.codes + key * D);
+    v.q = kv_ld16(vb.codes + key * D);
+    k.e = kb.scales[key * (D / 32)];
+    v.e = vb.scales[key * (D / 32)];
+  }
+  static __device__ __forceinline__ void unpack(const Raw& r, float (&f)[E]) { kv8_unpack(r.q, f); }
+  static __device__ __forceinline__ float dot(const float (&q)[E], const float (&kx)[E], const Raw& r) {
+    float a = 0.f;
 #pragma unroll
-  for (int i = 0; i < kKv8E; ++i) out[i] = Elem<T>::round(Elem<T>::round(own[i] * cs[i]) + Elem<T>::round((upper ? par[i] : -par[i]) * sn[i]));
-}
-
-// sum over the LPK (4 or 8) aligned lanes that share one key: DPP only
-template <int LPK>
-__device__ __forceinline__ float kv8_lpk_sum(float a) {
-  static_assert(LPK == 4 || LPK == 8, "head_dim 64 or 128");
-  a += dpp_f32<kDppXor1>(a);
-  a += dpp_f32<kDppXor2>(a);
-  if constexpr (LPK == 8) a += dpp_f32<kDppHalfMirror>(a);
-  return a;
-}
+    for (int i = 0; i < E; ++i) a = fmaf(q[i], kx[i], a);
+    return a * mx8_pow2(r.e);  // the block's 2^e on the fp32 partial
+  }
+  static __device__ __forceinline__ void axpy(bool ok, float p, const float (&vx)[E], const Raw& r, float (&o)[E]) {
+    const float ps = p * mx8_pow2(r.e);  // p * 2^e: exact
+#pragma unroll
+    for (int i = 0; i < E; ++i) o[i] = ok ? fmaf(ps, vx[i], o[i]) : o[i];
+  }
+};
 
 // quantise the 16 elements this lane holds of a row (its neighbour, lane ^ 1, holds the other half of the scale block) and store codes + scale byte
 template <int D>
@@ -92,15 +112,16 @@ __device__ __forceinline__ void kv8_store_row(const float (&x)[kKv8E], int e_min
   if (writes_scale) *scale_byte = (uint8_t)(e + 127);
 }
 
-// grid (n_splits, n_heads, B), NW waves.  stride_b / stride_h: of the code planes (bytes = elements); the scale planes' are 1/32 of them.
+// grid (n_splits, n_heads, B), NW waves.  attn_decode_split_kernel's sequence with its own finish: the new token opens its lane group's softmax.
 template <typename T, int D, int NW, int U>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(
     const void* __restrict__ qkv_, int64_t q_row_stride, uint8_t* kq_, uint8_t* ksc_, uint8_t* vq_, uint8_t* vsc_, int64_t stride_b, int64_t stride_h,
     const int32_t* __restrict__ kv_len, float* __restrict__ ws, void* __restrict__ out_, int64_t out_row_stride, int n_rep, float scale,
     const void* __restrict__ cos_, const void* __restrict__ sin_, int n_pos, const int32_t* __restrict__ pos_base, int T_cap, int n_kv_heads, int chunk_keys,
     int e_min) {
+  using St = AttnSplitState<T, D, NW, U, KvMx8Rows>;
   using S = typename Elem<T>::storage;
-  constexpr int E = kKv8E, LPK = D / E, KPW = 64 / LPK, NG = NW * KPW, HALF = D / 2, NSB = D / 32;
+  constexpr int E = St::E, LPK = St::LPK, NG = St::NG, HALF = D / 2, NSB = D / 32;
   static_assert(NW * 64 >= D, "the D finishing threads");
   __shared__ float sm_m[NG], sm_l[NG];
   __shared__ __attribute__((aligned(16))) float sm_o[NG * D];
@@ -108,76 +129,23 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(
   const int split = blockIdx.x, n_splits = gridDim.x, h = blockIdx.y;
   const int n_heads = gridDim.y;
   const int tid = threadIdx.x;
-  // ragged batches, longest row first: attn_decode_split_kernel's ranking (slice z of the grid takes the row with the z-th largest length)
-  int b = blockIdx.z;
-  int T_ranked = -1;
-  if (gridDim.z > 1 && gridDim.z <= 64) {
-    const int ln = tid & 63, Bn = (int)gridDim.z;
-    const int my = ln < Bn ? kv_len[ln] : -1;
-    int rank = 0;
-    for (int j = 0; j < Bn; ++j) {
-      const int lj = __builtin_amdgcn_readlane(my, j);
-      rank += (lj > my || (lj == my && j < ln)) ? 1 : 0;
-    }
-    const unsigned long long mk = __ballot(ln < Bn && rank == (int)blockIdx.z);
-    b = __builtin_amdgcn_readfirstlane(__builtin_ctzll(mk));
-    T_ranked = __builtin_amdgcn_readlane(my, b);
-  }
+  int b, T_ranked;  // ragged batches, longest row first
+  attn_rank_row(kv_len, b, T_ranked);
   const int kvh = h / n_rep;
-  const int lane = tid & 63, wid = tid >> 6, g = lane / LPK, c = (lane % LPK) * E;
-  const int64_t code_off = (int64_t)b * stride_b + (int64_t)kvh * stride_h;
-  const int64_t sc_off = (int64_t)b * (stride_b >> 5) + (int64_t)kvh * (stride_h >> 5);
-  uint8_t* const kq = kq_ + code_off + c;
-  uint8_t* const vq = vq_ + code_off + c;
-  uint8_t* const ksc = ksc_ + sc_off + (c >> 5);
-  uint8_t* const vsc = vsc_ + sc_off + (c >> 5);
-
-  uint4 kraw[U], vraw[U];
-  uint32_t ke[U], ve[U];  // the scale bytes of the lane's block
-  bool ok[U];
-#define KV8_REQ(key_, k_, v_, ke_, ve_)                      \
-  do {                                                       \
-    const int64_t key__ = (key_);                            \
-    k_ = kv_ld16(kq + key__ * D);                            \
-    v_ = kv_ld16(vq + key__ * D);                            \
-    ke_ = ksc[key__ * NSB];                                  \
-    ve_ = vsc[key__ * NSB];                                  \
-  } while (0)
-
-  // ---- every load that does not depend on another load first (attn_split_issue) ----
-  const bool spec = chunk_keys > 0;
-  int chunk = 0, k0 = 0;
-  if (spec) {  // the key range does not depend on kv_len: any slot < T_cap is readable, masked once the length has arrived
-    chunk = (chunk_keys + NG - 1) / NG * NG;
-    k0 = split * chunk;
-#pragma unroll
-    for (int u = 0; u < U; ++u) KV8_REQ(min(k0 + (u * NW + wid) * KPW + g, T_cap - 1), kraw[u], vraw[u], ke[u], ve[u]);
-  }
   const int T_old = T_ranked >= 0 ? T_ranked : kv_len[b];
-  const int Tn = T_old + 1;
-  if (!spec) {
-    chunk = (Tn + n_splits - 1) / n_splits;
-    chunk = (chunk + NG - 1) / NG * NG;
-    k0 = split * chunk;
-  }
-  // this split's keys [k0, k1s); with a host chunk the last split also takes whatever the host's length bound missed
-  const int k1s = (spec && split == n_splits - 1) ? Tn : min(Tn, k0 + chunk);
-  const int k1 = min(k1s, T_old);  // ... of which [k0, k1) are read from the planes
-#pragma unroll
-  for (int u = 0; u < U; ++u) {
-    const int key = k0 + (u * NW + wid) * KPW + g;
-    ok[u] = key < k1;
-    if (!spec) KV8_REQ(ok[u] ? key : (k0 < k1 ? k0 : 0), kraw[u], vraw[u], ke[u], ve[u]);
-  }
+  St st;
+  attn_split_issue<T, D, NW, true, U>(st, tid, KvMx8Rows::Slab{kq_, ksc_}, KvMx8Rows::Slab{vq_, vsc_}, stride_b, stride_h, T_old, 1, b, kvh, split, n_splits, T_cap,
+                                      chunk_keys);
 
   // ---- RoPE of q; the new token's key / value for the lane group that owns key index T_old ----
   const char* row = reinterpret_cast<const char*>(qkv_) + (int64_t)b * q_row_stride * (int64_t)sizeof(S);
   const S* qrow = reinterpret_cast<const S*>(row) + (int64_t)h * D;
   const S* krow = reinterpret_cast<const S*>(row) + (int64_t)(n_heads + kvh) * D;
   const S* vrow = reinterpret_cast<const S*>(row) + (int64_t)(n_heads + n_kv_heads + kvh) * D;
+  const int c = st.c;
   const bool upper = c >= HALF;
   const int cpar = upper ? c - HALF : c + HALF;
-  const bool owns_new = T_old >= k0 && T_old < k1s && wid == 0 && g == 0;
+  const bool owns_new = T_old >= st.k0 && T_old < st.k1s && st.wid == 0 && st.g == 0;
   float qv[E], cs[E], sn[E], kn[E], vn[E];
   {
     int p = pos_base[b];
@@ -191,126 +159,40 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(
       kv8_load_row<T>(krow + c, kown);
       kv8_load_row<T>(krow + cpar, kpar);
       kv8_load_row<T>(vrow + c, vn);
-      kv8_rope<T>(upper, kown, kpar, cs, sn, kn);
+      rope16<T>(upper, kown, kpar, cs, sn, kn);
     }
     // q's partner half (column c +- D/2) is what the lane LPK / 2 lanes away in this lane group has just loaded
 #pragma unroll
     for (int i = 0; i < E; ++i) par[i] = __shfl_xor(own[i], LPK / 2);
-    kv8_rope<T>(upper, own, par, cs, sn, qv);
+    rope16<T>(upper, own, par, cs, sn, qv);
   }
 
-  // ---- online softmax over the slab keys [k0, k1): per lane group (m, l, o[16]); keys dealt round-robin, trip i + 1 requested before trip i is consumed ----
-  float m = -INFINITY, l = 0.f, o[E];
-#pragma unroll
-  for (int i = 0; i < E; ++i) o[i] = 0.f;
+  // ---- online softmax per lane group (m, l, o[16]) ----
+  float m, l, o[E];
+  attn_softmax_open(m, l, o);
   // the new token (key index T_old) opens its lane group's softmax: exact in the model dtype for this step, stored quantised for the later ones.  (Folding it
   // in before the slab keys instead of after them -- attn_split_finish's order -- frees its 32 registers for the loop and puts the quantiser under the first
   // trip's memory latency; the online softmax gives the same value up to fp32 rounding.)
   if (owns_new) {
     if (h % n_rep == 0 && T_old < T_cap) {  // one writer per kv head; eviction = the length is simply not advanced later
-      kv8_store_row<D>(kn, e_min, kq + (int64_t)T_old * D, ksc + (int64_t)T_old * NSB, (lane & 1) == 0);
-      kv8_store_row<D>(vn, e_min, vq + (int64_t)T_old * D, vsc + (int64_t)T_old * NSB, (lane & 1) == 0);
+      const bool writes_scale = (st.lane & 1) == 0;
+      kv8_store_row<D>(kn, e_min, st.kb.codes + (int64_t)T_old * D, st.kb.scales + (int64_t)T_old * NSB, writes_scale);
+      kv8_store_row<D>(vn, e_min, st.vb.codes + (int64_t)T_old * D, st.vb.scales + (int64_t)T_old * NSB, writes_scale);
     }
     float a = 0.f;
 #pragma unroll
     for (int i = 0; i < E; ++i) a = fmaf(qv[i], kn[i], a);
-    a = kv8_lpk_sum<LPK>(a);
+    a = lpk_sum<LPK>(a);
     m = a * scale;
     l = 1.f;
 #pragma unroll
     for (int i = 0; i < E; ++i) o[i] = vn[i];
   }
-  uint4 kpre[U], vpre[U];
-  uint32_t kepre[U], vepre[U];
-  bool okpre[U];
-  for (int base = k0; base < k1; base += NG * U) {
-    const int nbase = base + NG * U;
-    if (nbase < k1) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int key = nbase + (u * NW + wid) * KPW + g;
-        okpre[u] = key < k1;
-        KV8_REQ(okpre[u] ? key : k0, kpre[u], vpre[u], kepre[u], vepre[u]);
-      }
-    }
-    float sc[U];
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-      float kx[E];
-      kv8_unpack(kraw[u], kx);
-      float a = 0.f;
-#pragma unroll
-      for (int i = 0; i < E; ++i) a = fmaf(qv[i], kx[i], a);
-      a *= mx8_pow2(ke[u]);  // the block's 2^e on the fp32 partial
-      a = kv8_lpk_sum<LPK>(a);
-      sc[u] = ok[u] ? a * scale : -INFINITY;  // a select: a masked slot may have produced NaN / Inf
-    }
-    float mn = m;
-#pragma unroll
-    for (int u = 0; u < U; ++u) mn = fmaxf(mn, sc[u]);
-    if (mn > -INFINITY) {
-      const float alpha = __expf(m - mn);  // m = -inf -> 0
-      l *= alpha;
-#pragma unroll
-      for (int i = 0; i < E; ++i) o[i] *= alpha;
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        float vx[E];
-        kv8_unpack(vraw[u], vx);
-        const float p = __expf(sc[u] - mn);  // masked key: exp(-inf) = 0
-        l += p;
-        const float ps = p * mx8_pow2(ve[u]);  // p * 2^e: exact
-#pragma unroll
-        for (int i = 0; i < E; ++i) o[i] = ok[u] ? fmaf(ps, vx[i], o[i]) : o[i];
-      }
-      m = mn;
-    }
-    if (nbase < k1) {
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        kraw[u] = kpre[u];
-        vraw[u] = vpre[u];
-        ke[u] = kepre[u];
-        ve[u] = vepre[u];
-        ok[u] = okpre[u];
-      }
-    }
-  }
-#undef KV8_REQ
+  attn_split_keys(st, qv, scale, m, l, o);  // the slab keys [k0, k1)
 
-  // ---- merge the NG lane groups through LDS -> (M, L, O) for threads tid < D ----
-  const int gg = wid * KPW + g;
-  if ((lane % LPK) == 0) {
-    sm_m[gg] = m;
-    sm_l[gg] = l;
-  }
-#pragma unroll
-  for (int i = 0; i < E; i += 4) *reinterpret_cast<float4*>(sm_o + gg * D + c + i) = make_float4(o[i], o[i + 1], o[i + 2], o[i + 3]);
-  __syncthreads();
-  if (tid < D) {
-    float M = -INFINITY;
-#pragma unroll 8
-    for (int i = 0; i < NG; ++i) M = fmaxf(M, sm_m[i]);
-    float L = 0.f, O = 0.f;
-    if (M > -INFINITY) {
-#pragma unroll 8
-      for (int i = 0; i < NG; ++i) {
-        const float w = __expf(sm_m[i] - M);  // empty group: exp(-inf) = 0
-        L += sm_l[i] * w;
-        O += sm_o[i * D + tid] * w;
-      }
-    }
-    if (n_splits == 1) {
-      store1<T>(out_, (int64_t)b * out_row_stride + (int64_t)h * D + tid, L > 0.f ? O / L : 0.f);
-    } else {
-      float* pw = ws + (((int64_t)b * n_heads + h) * n_splits + split) * (D + kAttnPartPad);
-      pw[kAttnPartPad + tid] = O;
-      if (tid == 0) {
-        pw[0] = M;
-        pw[1] = L;
-      }
-    }
-  }
+  float M, L, O;
+  attn_split_lds_merge(st, tid, m, l, o, sm_m, sm_l, sm_o, M, L, O);
+  if (tid < D) attn_store_partial<T, D>(tid, b, h, n_heads, split, n_splits, M, L, O, ws, out_, out_row_stride);
 }
 
 template <typename T, int D, int NW, int U>

@@ -278,10 +278,11 @@ def build_decode(kernel, dist_entry, dtype, nH, nKV, d, seed=0):
     return qkv, k0, v0, cos, sin
 
 
-def run_decode(ops, kernel, dist_entry, dtype, nH, nKV, d, seed=0, launches=None):
+def run_decode(ops, kernel, dist_entry, dtype, nH, nKV, d, seed=0, launches=None, outputs=None):
     """Every launch form of `kernel` ("decode": dl_attn_decode, "rope": dl_attn_decode_rope, "parts": dl_attn_decode_rope_parts) on one batch.
     The rotated query and the slab after the append come from dl_rope_kv_write; the fused kernels' slabs must equal them bit for bit.
-    Returns {launch: (worst ratio, worst ulps, where)}."""
+    Returns {launch: (worst ratio, worst ulps, where)}.  `outputs`: as in run_prefill -- per launch the output slice and, for the fused kernels, the
+    K and V rows the launch appended."""
     qkv, k0, v0, cos, sin = build_decode(kernel, dist_entry, dtype, nH, nKV, d, seed)
     B = len(DECODE_KV_LEN)
     lens = torch.tensor(DECODE_KV_LEN, dtype=torch.int32).cuda()
@@ -298,7 +299,9 @@ def run_decode(ops, kernel, dist_entry, dtype, nH, nKV, d, seed=0, launches=None
         ops.rope_kv_write(qa, cosd, sind, cu, None, posd, lens, ka, va, nH, nKV, d)
     torch.cuda.synchronize()
     q_ref, k_ref, v_ref = qa.cpu()[:, : nH * d].view(B, nH, d), ka.cpu(), va.cpu()
-    truths = [at.truth(q_ref[b][None], k_ref[b, :, : T + 1].transpose(0, 1), v_ref[b, :, : T + 1].transpose(0, 1), heads=_heads(nH)) for b, T in enumerate(DECODE_KV_LEN)]
+    truths = [] if outputs is not None else [
+        at.truth(q_ref[b][None], k_ref[b, :, : T + 1].transpose(0, 1), v_ref[b, :, : T + 1].transpose(0, 1), heads=_heads(nH)) for b, T in enumerate(DECODE_KV_LEN)]
+    rows = torch.arange(B, device="cuda")
     ws = ops.attn_decode_workspace(B, nH, d, 32, "cuda")
     res = {}
     for launch in (decode_launches(kernel) if launches is None else launches):
@@ -324,6 +327,10 @@ def run_decode(ops, kernel, dist_entry, dtype, nH, nKV, d, seed=0, launches=None
         w = out.cpu()
         assert bool(torch.isnan(w[:, :PAD_COLS]).all()) and bool(torch.isnan(w[:, PAD_COLS + nH * d :]).all()), f"{kernel} {launch}: written outside the output slice"
         got = w[:, PAD_COLS : PAD_COLS + nH * d].reshape(B, nH, d)
+        if outputs is not None:
+            outputs.append(got.contiguous())
+            if kernel != "decode":
+                outputs.extend(x[rows, :, lens.long()].cpu().contiguous() for x in (kb, vb))
         worst = (0.0, 0.0, "")
         for b, t in enumerate(truths):
             r, ulps, i = at.worst_ratio(got[b][None][:, t.heads], t, d, dtype)
@@ -340,10 +347,11 @@ QKV_ATTN_T_OLD = [0, 37, 199, 300, 700]
 QKV_ATTN_DISTS = ("sink", "late_peak", "newtok", "newtok_mirror", "v_outlier")
 
 
-def run_qkv_attn(ops, dist, dtype, nH, nKV, d, H, T_old, seed=0):
+def run_qkv_attn(ops, dist, dtype, nH, nKV, d, H, T_old, seed=0, outputs=None):
     """dl_gemv_qkv_attn with 1..4 attention workgroups per head on a planted slab.  The projection's output is the kernel's own (bit-equal to
     dl_gemv's, asserted); the slab is planted relative to the rotated query it implies; truth = the attention the launch performs.
-    Returns {n_splits: (worst ratio, worst ulps, where)}."""
+    Returns {n_splits: (worst ratio, worst ulps, where)}.  `outputs`: as in run_prefill -- of the two launches and of every n_splits the attention
+    output and the appended K and V rows; the truth is not evaluated."""
     g = torch.Generator().manual_seed(1000 * seed + T_old)
     rnd = lambda *shape, s=0.02: (torch.randn(*shape, generator=g) * s).to(dtype).cuda()
     N = (nH + 2 * nKV) * d
@@ -370,10 +378,14 @@ def run_qkv_attn(ops, dist, dtype, nH, nKV, d, H, T_old, seed=0):
     out_r = torch.zeros(1, nH * d, dtype=dtype, device="cuda")
     ops.attn_decode_rope(qkv_r, cosd, sind, pos, lens, k_r, v_r, out_r, None, 1, nH, nKV, d, chunk_keys=256)
     torch.cuda.synchronize()
-    t = at.truth(q_rot[None], k_r.cpu()[0, :, : T_old + 1].transpose(0, 1), v_r.cpu()[0, :, : T_old + 1].transpose(0, 1))
     err = torch.zeros(1, dtype=torch.int32, device="cuda")
     gran = ops.gemv_qkv_attn_workspace(nH, nKV, d, "cuda")
-    res = {"two launches": at.worst_ratio(out_r.cpu().view(1, nH, d), t, d, dtype)}
+    if outputs is not None:
+        outputs.extend(x.cpu().contiguous() for x in (out_r, k_r[0, :, T_old], v_r[0, :, T_old]))
+        t, res = None, {}
+    else:
+        t = at.truth(q_rot[None], k_r.cpu()[0, :, : T_old + 1].transpose(0, 1), v_r.cpu()[0, :, : T_old + 1].transpose(0, 1))
+        res = {"two launches": at.worst_ratio(out_r.cpu().view(1, nH, d), t, d, dtype)}
     for ns in (1, 2, 3, 4):
         k_f, v_f = k0.cuda(), v0.cuda()
         qkv_f, ho_f, out_f = torch.zeros_like(qkv_r), torch.zeros_like(ho_r), torch.full((1, nH * d), float("nan"), dtype=dtype, device="cuda")
@@ -381,6 +393,9 @@ def run_qkv_attn(ops, dist, dtype, nH, nKV, d, H, T_old, seed=0):
         torch.cuda.synchronize()
         assert torch.equal(qkv_f, qkv_r) and torch.equal(ho_f, ho_r), f"n_splits {ns}: projection row / residual stream differ from dl_gemv's"
         assert torch.equal(k_f.nan_to_num(7.0), k_r.nan_to_num(7.0)) and torch.equal(v_f.nan_to_num(7.0), v_r.nan_to_num(7.0)), f"n_splits {ns}: appended K/V row"
+        if outputs is not None:
+            outputs.extend(x.cpu().contiguous() for x in (out_f, k_f[0, :, T_old], v_f[0, :, T_old]))
+            continue
         r, ulps, i = at.worst_ratio(out_f.cpu().view(1, nH, d), t, d, dtype)
         res[ns] = (r, ulps, f"head {i // d} dim {i % d}")
     assert int(err.item()) == 0, "a consumer gave up waiting"

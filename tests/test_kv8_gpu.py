@@ -302,7 +302,9 @@ def test_exhaustive_dequantisation_of_k_through_the_score(dtype, d):
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # 5. hard inputs, every launch form
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
-def _run_hard(dist, dtype, nH, nKV, d, forms=LAUNCH_FORMS):
+def _run_hard(dist, dtype, nH, nKV, d, forms=LAUNCH_FORMS, outputs=None):
+    """`outputs`: a list that receives, per launch form, the output slice and the appended rows of the four planes; the truth is then not evaluated
+    (tools/attn_error_table.py --digest)."""
     qkv, k0, v0, cos, sin = ac.build_decode("rope", dist, dtype, nH, nKV, d)
     B, T_cap = len(ac.DECODE_KV_LEN), ac.DECODE_T_CAP
     lens = torch.tensor(ac.DECODE_KV_LEN, dtype=torch.int32).cuda()
@@ -325,7 +327,8 @@ def _run_hard(dist, dtype, nH, nKV, d, forms=LAUNCH_FORMS):
         k_new, v_new = k_rot[b, :, T], v_rot[b, :, T]  # [nKV, d]
         kk = torch.cat([_dq_rows(kq, ks, dtype).transpose(0, 1), k_new[None]])  # [T + 1, nKV, d]
         vv = torch.cat([_dq_rows(vq, vs, dtype).transpose(0, 1), v_new[None]])
-        truths.append(at.truth(q_ref[b][None], kk, vv, heads=ac._heads(nH)))
+        if outputs is None:
+            truths.append(at.truth(q_ref[b][None], kk, vv, heads=ac._heads(nH)))
     for v_, e_ in zip(pl0.views, exp):
         v_.copy_(e_.cuda())
     for b, T in enumerate(ac.DECODE_KV_LEN):  # after the launch: the appended codes and scales = quantize_mx8 of dl_rope_kv_write's rotated key row and value row
@@ -347,6 +350,9 @@ def _run_hard(dist, dtype, nH, nKV, d, forms=LAUNCH_FORMS):
             assert torch.equal(got.cpu(), want), f"{form}: {name} after the append (appended row = quantize_mx8 of the rotated row; every other slot unchanged)"
         assert pl.guards_intact(), form
         got = w[:, ac.PAD_COLS : ac.PAD_COLS + nH * d].reshape(B, nH, d)
+        if outputs is not None:
+            outputs.append(got.contiguous())
+            outputs.extend(x[torch.arange(B, device="cuda"), :, lens.long()].cpu().contiguous() for x in pl.views)
         worst = (0.0, 0.0, "")
         for b, t in enumerate(truths):
             r, ulps, i = at.worst_ratio(got[b][None][:, t.heads], t, d, dtype)
