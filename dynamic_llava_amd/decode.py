@@ -25,12 +25,13 @@ class StepMode:
     processed: bool = False  # dl_logits_process in front of the kernel; an all-neutral request is exactly the request without the keywords
     logprobs: int = -1  # dl_decode_logprobs behind the kernel: generate(output_logprobs=True, top_logprobs=n) -- -1: off, else n
     stop: bool = False  # dl_decode_stop as the last launch: generate(stop_sequences= / stopping_criteria=[keyword criterion]); the list itself is device data
+    constrained: bool = False  # dl_logits_constrain in front of the kernel: generate(constraint= / guided_choice= / allowed_token_ids=); the automaton itself is device data
 
     @classmethod
     def of(cls, req, max_new):
         """The mode of a parsed request (request.Request) of max_new steps; the one place the EOS tuple becomes the kernels' -1 / id / tuple."""
         return cls(eos=-1 if not req.eos else (req.eos[0] if len(req.eos) == 1 else req.eos), pad=req.pad, min_new=min(req.min_new, max_new), sampled=req.sampled is not None,
-                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp, stop=bool(req.stops))
+                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp, stop=bool(req.stops), constrained=req.constraint is not None)
 
 
 class _DecodeState:
@@ -110,6 +111,9 @@ class _DecodeState:
         # dl_decode_stop's table (generate(stop_sequences=)): device memory the captured launch reads, rewritten by generate() before the first launch of such a
         # request, like sample_params -- one graph serves every stop list
         self.stop_table = ops.stop_table_block(device)
+        # dl_logits_constrain's automaton, start states and state history (generate(constraint= / guided_choice= / allowed_token_ids=)): made by need_constraint() on
+        # the first such request and with the state thereafter; rewritten by generate() before the first launch of a constrained request -- one graph serves every automaton
+        self.con_table = self.con_start = self.con_hist = None
         self.tok_host = None  # generate(streamer=): ring of pinned token words beside obs_host, made by need_stream() on the first such request
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
@@ -142,6 +146,14 @@ class _DecodeState:
             self.top_lp = torch.zeros((B, cap, MAX_TOP_LOGPROBS), dtype=torch.float32, device=dev)
             self.top_ids = torch.full((B, cap, MAX_TOP_LOGPROBS), -1, dtype=torch.int64, device=dev)
 
+
+    def need_constraint(self):
+        """Allocates dl_logits_constrain's table, start states and state history once per state (the captured launches hold their pointers)."""
+        if self.con_table is None:
+            B, cap, dev = *self.out_ids.shape, self.out_ids.device
+            self.con_table = ops.constraint_table_block(dev)
+            self.con_start = torch.full((B,), -1, dtype=torch.int32, device=dev)
+            self.con_hist = torch.full((B, cap + 1), -1, dtype=torch.int32, device=dev)  # slot j: the state in which token j is chosen
 
     def need_stream(self, chunk):
         """The pinned ring the chunks' tokens leave through (generate(streamer=)): 4 slots of B x chunk int64 words, one per observation in flight."""
@@ -205,6 +217,10 @@ class DecodeScheduler:
             if m.forced:
                 raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
             logits = ops.logits_process(st.logits, st.proc_logits, st.logits_params, st.out_ids, st.step, st.bad_words)
+        if m.constrained:  # generate() with a constraint: behind the processors (HF's order), every token without an edge out of the row's state becomes -inf; st.logits is never written
+            if m.forced:
+                raise ValueError("score() takes no constraint: a label is scored on the model's own logits")
+            logits = ops.logits_constrain(logits, st.proc_logits, st.con_table, st.con_start, st.con_hist, st.out_ids, st.step)
         if m.forced:  # score(): the same bookkeeping around the label, scored
             ops.decode_score(st.logits, st.cur_ids, st.labels, st.nll, st.top1, st.out_ids, st.step, st.finished, m.pad, lf, ls, dec)
         elif m.sampled:  # generate(do_sample=True, seed=...): the same bookkeeping around a sampled token
@@ -513,6 +529,11 @@ class DecodeScheduler:
             st.bad_words.copy_(ops.bad_words_table(req.rules.bad_words, "cpu"))
         if req.stops:
             st.stop_table.copy_(ops.stop_table_words(req.stops))
+        if req.constraint is not None:
+            st.need_constraint()
+            ops.constraint_table_write(st.con_table, *req.constraint.words())
+            st.con_start.copy_(torch.tensor(req.constraint.starts(st.B // req.constraint.n_return), dtype=torch.int32))
+            st.con_hist.fill_(-1)  # DONE: a slot no launch of this request reaches shows no earlier request's state
         if req.forced is not None:
             st.labels.fill_(IGNORE_INDEX)
             st.labels[:, : req.forced.shape[1]].copy_(req.forced)
@@ -574,7 +595,7 @@ class DecodeScheduler:
         key = (cache.slab.data_ptr(), cache.t_cap, splits, fused_ns, self._rope[0].data_ptr(),
                repr(cfg.sparse_config), self.attn_inkernel_combine, self.tp_side_stream, self.smallm_max_decode_batch, self.gemv_max_decode_batch, self.fuse_qkv_attn, self.fuse_gu_tp, KVSlabCache.eight_wave_single_split,
                self.decode_weight_pack, self.decode_weight_pack_plain, self.decode_weight_pack_qkv, self.decode_weight_pack_down, self.fused_attn_max_splits, self.qkv_attn_grid_cap, self.gu_grid_cap, self.packed_decode_qkv_min_batch, self.packed_decode_qkv_parts, self.packed_decode_qkv_parts_max_batch, self.decode_weight_format, self.mx8_max_decode_batch,
-               self._kv_format_key(cache), self._mode)  # (the mode: sampled, scored or greedy -- which bookkeeping kernel was captured, its constants, and whether dl_logits_process runs in front of it; the sampling parameters, the labels and the processors' settings are device data, not part of the key)
+               self._kv_format_key(cache), self._mode)  # (the mode: sampled, scored or greedy -- which bookkeeping kernel was captured, its constants, and whether dl_logits_process runs in front of it; the sampling parameters, the labels, the processors' settings and the automaton of a constraint are device data, not part of the key)
         if not self.use_hip_graph:
             for _ in range(n_steps):
                 self._decode_step_kernels(st, cache, True)

@@ -172,6 +172,7 @@ SIGNATURES = {
         [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p],
     ),
     "dl_logits_process": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dl_logits_constrain": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_decode_logprobs": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dl_decode_stop": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
@@ -1068,6 +1069,60 @@ def logits_process(logits, out, params, out_ids=None, step=None, bad_words=None)
     _check(
         lib().dl_logits_process(_p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(out), _p(out_ids), out_cap, _p(step), _p(params), _p(bad_words), _stream()),
         "dl_logits_process",
+    )
+    return out
+
+
+CONSTRAIN_MAX_STATES, CONSTRAIN_MAX_EDGES = 4096, 131072  # include/dynllava.h DL_CONSTRAIN_MAX_STATES / _EDGES (constraints.MAX_STATES / MAX_EDGES)
+CONSTRAIN_HEADER_WORDS = 8  # dl_constraint_table: n_states, n_edges, 6 reserved words, then state_ptr[MAX_STATES + 1], then edges[MAX_EDGES][2]
+CONSTRAIN_TABLE_WORDS = CONSTRAIN_HEADER_WORDS + CONSTRAIN_MAX_STATES + 1 + 2 * CONSTRAIN_MAX_EDGES
+
+
+def constraint_table_block(device):
+    """Device memory for one dl_constraint_table (zeroed: n_states 0, which makes every row DONE -- the launch then copies the logits through)."""
+    return torch.zeros(CONSTRAIN_TABLE_WORDS, dtype=torch.int32, device=device)
+
+
+def constraint_table_write(block, state_ptr, edges):
+    """Writes an automaton into a dl_constraint_table block (a CPU or DEVICE int32 [CONSTRAIN_TABLE_WORDS] tensor), before the first launch of a request: the
+    header, state_ptr (int32 [n_states + 1]) and edges (int32 [n_edges, 2], (token, next)).  Only the words in use are copied -- the kernel reads nothing past
+    state_ptr[n_states] and edges[n_edges], so what an earlier request left behind them is never seen."""
+    n_states, n_edges = int(state_ptr.numel()) - 1, int(edges.shape[0])
+    if not (1 <= n_states <= CONSTRAIN_MAX_STATES and 0 <= n_edges <= CONSTRAIN_MAX_EDGES):
+        raise HipOpsError(f"constraint_table_write: {n_states} states and {n_edges} edges: dl_logits_constrain takes {CONSTRAIN_MAX_STATES} and {CONSTRAIN_MAX_EDGES}")
+    assert block.dtype == torch.int32 and block.numel() >= CONSTRAIN_TABLE_WORDS and block.is_contiguous()
+    assert state_ptr.dtype == torch.int32 and edges.dtype == torch.int32 and (n_edges == 0 or edges.shape[1] == 2)
+    head = torch.zeros(CONSTRAIN_HEADER_WORDS + n_states + 1, dtype=torch.int32)
+    head[0], head[1] = n_states, n_edges
+    head[CONSTRAIN_HEADER_WORDS:] = state_ptr
+    block[: head.numel()].copy_(head)
+    e0 = CONSTRAIN_HEADER_WORDS + CONSTRAIN_MAX_STATES + 1
+    block[e0 : e0 + 2 * n_edges].copy_(edges.reshape(-1))
+    return block
+
+
+def logits_constrain(logits, out, table, start, state_hist, out_ids=None, step=None):
+    """The constraint of one step (include/dynllava.h, constraints.py): logits [B, V] (any row stride) -> out fp32 [B, V], contiguous; out may be `logits` itself
+    (fp32, contiguous).  table: int32 [CONSTRAIN_TABLE_WORDS] DEVICE tensor holding a dl_constraint_table; start int32 [B]; state_hist int32 [B, out_cap + 1];
+    out_ids int64 [B, out_cap] + step int32 [B]: the rows' tokens so far (None: step 0)."""
+    _dev(logits, out, table, start, state_hist, out_ids, step)
+    assert logits.dim() == 2 and logits.stride(1) == 1
+    B, V = logits.shape
+    assert out.dtype == torch.float32 and out.shape == (B, V) and out.is_contiguous()
+    assert out.data_ptr() != logits.data_ptr() or (logits.dtype == torch.float32 and logits.is_contiguous()), "in place: fp32, contiguous"
+    if table is not None:  # (None reaches the library, which refuses it)
+        assert table.dtype == torch.int32 and table.numel() >= CONSTRAIN_TABLE_WORDS and table.is_contiguous()
+    out_cap = 0
+    if out_ids is not None:
+        assert out_ids.dtype == torch.int64 and out_ids.dim() == 2 and out_ids.shape[0] == B and out_ids.is_contiguous()
+        out_cap = out_ids.shape[1]
+    if step is not None:
+        assert step.dtype == torch.int32 and step.numel() == B and step.is_contiguous()
+    assert start.dtype == torch.int32 and start.numel() == B and start.is_contiguous()
+    assert state_hist.dtype == torch.int32 and state_hist.shape == (B, out_cap + 1) and state_hist.is_contiguous()
+    _check(
+        lib().dl_logits_constrain(_p(logits), dtype_code(logits.dtype), logits.stride(0), V, B, _p(out), _p(out_ids), out_cap, _p(step), _p(table), _p(start), _p(state_hist), _stream()),
+        "dl_logits_constrain",
     )
     return out
 

@@ -30,7 +30,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import logprobs, request, sampling, scoring, stopping
+from . import constraints, logprobs, request, sampling, scoring, stopping
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -537,7 +537,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         Token streams cannot match HF's draw for draw (different RNG consumption); the distribution per step is the same.
         repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process on every step's logits before anything else, on the tokens emitted in this call.
         output_logprobs / top_logprobs: logprobs.reference_rows on every step's raw fp32 logits (the rule dl_decode_logprobs implements), masked behind a row's EOS."""
-        req = request.parse(kwargs, self.config)
+        req = request.parse(kwargs, self.config, batch=inputs.shape[0])
         attention_mask, image_features = req.attention_mask, req.image_features
         if req.n_return > 1:  # n answers per prompt on a host route: every prompt n times in the batch (rows b * n .. b * n + n - 1, HF's order), no fork
             rep = lambda t: t.repeat_interleave(req.n_return, dim=0) if torch.is_tensor(t) else t
@@ -563,6 +563,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             res["scores"] = tuple(scores)
         if req.n_lp >= 0:
             res.update(logprobs.host_result(raw, seq, req.eos, req.n_lp, finish[0] if (req.stops or req.criteria) else None))
+        if req.constraint is not None:
+            res["constraint_complete"] = constraints.complete(req.constraint, seq.cpu()).to(seq.device)
         return res
 
     @torch.no_grad()
@@ -574,7 +576,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         chunk-on-cache path (DML:2506-2521: the instruct predictor decides which of its K/V rows stay in layers >= sparse_layer), the new
         tokens through single decode steps; plain loop over forward(), no hipGraph.  repetition_penalty / no_repeat_ngram_size / bad_words_ids: logits_rules.process
         on every step's logits, on the tokens emitted in this call."""
-        req = request.parse(kwargs, self.config)
+        req = request.parse(kwargs, self.config, batch=inputs.shape[0])
         if images is not None or req.image_features is not None:
             raise NotImplementedError("generate(past_key_values=...) continues a dialogue: the image belongs to the first call")
         cache = kwargs["past_key_values"]
@@ -599,7 +601,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         return self._host_decode(req, out.past_key_values, out.logits[:, -1].float(), max_new, True)
 
     @torch.no_grad()
-    def score(self, input_ids, labels, images=None, image_sizes=None, *, attention_mask=None, image_features=None, sync_every=None, output_logits=False):
+    def score(self, input_ids, labels, images=None, image_sizes=None, *, attention_mask=None, image_features=None, sync_every=None, output_logits=False, **kwargs):
         """Teacher-forced negative log-likelihood of a labelled continuation, on the device inside generate()'s captured graphs: the reference's
         generation-time perplexity driver (llava/dynamic_eval/model_lvis_for_ppl.py:136-191 -- forward, take the last position's logits, record the
         label, feed the label) with dl_decode_score where greedy decoding has dl_decode_advance (the rule is scoring.py).
@@ -611,6 +613,10 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         token of every scored step, -1 where there is no label), past_key_values (the caller's own: an independent copy of the cache, so the pooled slab and
         the graphs captured on it serve the next call of the same shape);
         output_logits=True adds logits: a tuple of fp32 [B, V], one per step (the step-by-step route of generate(output_logits=True), for tests)."""
+        if any(k in constraints.KEYWORDS for k in kwargs):  # (constrained decoding restricts what a row may say; a label sequence is scored as it stands)
+            raise ValueError(f"score() takes no constraint ({', '.join(k for k in kwargs if k in constraints.KEYWORDS)}): a label is scored on the model's own logits")
+        if kwargs:
+            raise TypeError(f"score() got an unexpected keyword argument {next(iter(kwargs))!r}")
         if not torch.is_tensor(input_ids) or input_ids.dim() != 2:
             raise ValueError("input_ids must be a tensor [B, W]")
         if self.config.vocab_size > sampling.MAX_VOCAB:
@@ -667,12 +673,23 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         first, then put(sequences[:, j].cpu()) for every column of the returned `sequences`, in order and once each, then end().  On the device route the first
         token is put after the prefill and a chunk's tokens when the loop consumes that chunk's observation (the same pinned, non-blocking copies; the schedule,
         the tokens and the captured graphs are those of the call without a streamer); sync_every=1 is the knob for token-by-token latency.
+        constraint= (a constraints.TokenAutomaton, or a list of B, one per prompt), guided_choice= (a list of token-id sequences: every row says exactly one of them,
+        then EOS), allowed_token_ids= (a whitelist) and prefix_allowed_tokens_fn= (HF's fn(batch_id, ids_1d) -> allowed ids, called with the tokens generated in this
+        call) -- at most one of the four: constrained decoding.  Every row walks a deterministic token automaton; at every step the tokens with no edge out of the
+        row's state are -inf, behind the logits processors above and in front of temperature, top-k, top-p and the pick (HF's order for
+        PrefixConstrainedLogitsProcessor); every accepting state takes the request's EOS ids.  The first three run on the device inside the same captured graphs
+        (dl_logits_constrain between dl_logits_process and the step-closing launch; the rule is constraints.py; the automaton is device data, one graph serves every
+        automaton) up to constraints.MAX_STATES / MAX_EDGES, past them -- and the callable always -- on the plain loop over forward() with the same rule.  `scores`
+        are the constrained logits, `logits` and the log-probabilities stay the model's own; with return_dict_in_generate the result has `constraint_complete`, bool
+        [rows]: the row ended through an EOS edge instead of being cut off by max_new_tokens.  A dead end, an EOS id that is an edge of an accepting state,
+        min_new_tokens > 0, two of the keywords, or any of them in score() raise ValueError before any launch; a row that processors and constraint together leave all
+        -inf is the caller's error, as in HF.
         Still ignored without a word: logits_processor, suppress_tokens, sequence_bias.
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
         the new token ids / pixels into static buffers."""
         self._check_ready()
-        req = request.parse(kwargs, self.config, self.decode_sync_every)  # every keyword is validated here, before any launch
+        req = request.parse(kwargs, self.config, self.decode_sync_every, batch=inputs.shape[0] if torch.is_tensor(inputs) and inputs.dim() == 2 else None)  # every keyword is validated here, before any launch
         if req.route == "on_cache":
             return self._generate_on_cache(inputs, images, **kwargs)
         if req.route == "host_sample":
@@ -730,7 +747,7 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
         if req.want_logits:
             raw_logits.append(z.clone())
-        if req.rules.on:  # what dl_logits_process left for this step's bookkeeping launch
+        if req.rules.on or req.constraint is not None:  # what dl_logits_process / dl_logits_constrain left for this step's bookkeeping launch
             z = st.proc_logits.clone()
         banned = list(req.eos) if step_idx < req.min_new else []
         if req.sampled is not None:  # z = logit / T with -inf outside the kept set, as HF reports a sampled step: on the host, with the contract's own arithmetic (sampling.py)
@@ -778,4 +795,6 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             res["logprobs"] = lp
             if n > 0:
                 res["top_logprobs"], res["top_logprob_ids"] = top_lp, top_ids
+        if req.constraint is not None:  # replayed on the host over `sequences`: a row is complete when it ended through an EOS edge
+            res["constraint_complete"] = constraints.complete(req.constraint, out.cpu()).to(out.device)
         return res

@@ -7,22 +7,23 @@ from typing import Any, Optional, Tuple
 
 import torch
 
-from . import logits_rules, logprobs, sampling, stopping
+from . import constraints, logits_rules, logprobs, sampling, stopping
 from .sampling import eos_ids  # the only resolver of eos_token_id; defined in that leaf module because sampling.device_route needs it too
 
 
-def route(kwargs, rules, vocab_size, default_eos) -> str:
+def route(kwargs, rules, vocab_size, default_eos, constraint_on_host=False) -> str:
     """Which body of generate() serves the kwargs (the table is in DESIGN.md): "device" (the captured graphs), "host_sample" (_generate_sample), "host_greedy"
     (_generate_sample(greedy=True), without do_sample / sync_every) or "on_cache" (_generate_on_cache).  Past the device caps -- logits_rules.MAX_*, or more EOS
     ids than the step-closing kernels compare, or stopping.MAX_STOPS / MAX_STOP_LEN -- a request takes the plain loop over forward(), which applies the same rule on
-    the host; so does a request with a stopping criterion that is a callable (stopping.host_criteria), which only the host can call."""
+    the host; so does a request with a stopping criterion that is a callable (stopping.host_criteria), which only the host can call.  constraint_on_host: the
+    request's constraint is past constraints.MAX_STATES / MAX_EDGES, or is prefix_allowed_tokens_fn=, a callable like those criteria."""
     sample = bool(kwargs.get("do_sample", False))
     if sample and not sampling.device_route(kwargs, vocab_size, default_eos):
         return "host_sample"  # (KNOWN DEFECT: with past_key_values too -- _generate_sample never reads them, the dialogue is dropped without a word)
     if kwargs.get("past_key_values") is not None:
         return "on_cache"
     past_stop_caps = bool(stopping.host_criteria(kwargs)) or not stopping.device_route(stopping.normalize(kwargs, vocab_size))
-    if (rules.on and not rules.device_route) or len(eos_ids(kwargs, default_eos)) > sampling.MAX_EOS_IDS or past_stop_caps:
+    if (rules.on and not rules.device_route) or len(eos_ids(kwargs, default_eos)) > sampling.MAX_EOS_IDS or past_stop_caps or constraint_on_host:
         return "host_sample" if sample else "host_greedy"
     return "device"
 
@@ -72,6 +73,8 @@ class Request:
     stops: Tuple[Tuple[int, ...], ...] = ()  # stop_sequences= and the keyword criteria of stopping_criteria= (stopping.normalize): a row finishes when its tokens end in one
     criteria: tuple = ()  # the other items of stopping_criteria=: callables, served by the host loop only
     streamer: Any = None  # put(tensor) / end(): receives the tokens as they come (stopping.Feed)
+    constraint: Any = None  # constraint= / guided_choice= / allowed_token_ids=, compiled (constraints.Table): every row walks it, tokens without an edge are -inf
+    allowed_fn: Any = None  # prefix_allowed_tokens_fn=: fn(batch_id, ids_1d) -> the allowed ids, served by the host loop only
 
     @property
     def can_finish(self) -> bool:
@@ -88,9 +91,10 @@ class Request:
         return int(n)
 
 
-def parse(kwargs, config, sync_every=None) -> Request:
+def parse(kwargs, config, sync_every=None, batch=None) -> Request:
     """generate()'s **kwargs -> Request.  Every keyword is validated here, before any device work, in this order: the logits processors, score() with
-    processors, the stop sequences and criteria, score() with those, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences, the sampling parameters."""
+    processors, the stop sequences and criteria, score() with those, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences,
+    the constraint (batch: the number of prompts, which a list of automata must match), the sampling parameters."""
     V, eos = config.vocab_size, eos_ids(kwargs, config.eos_token_id)
     rules = logits_rules.normalize(kwargs, V, eos)  # (a one-token bad word equal to an EOS id is dropped, as in HF)
     forced = kwargs.get("_score_labels")
@@ -108,7 +112,8 @@ def parse(kwargs, config, sync_every=None) -> Request:
     if (kwargs.get("num_beams", 1) or 1) != 1:
         raise NotImplementedError("beam search is not built (harness default num_beams=1)")
     n_return = return_sequences(kwargs)
-    rt, sampled = route(kwargs, rules, V, config.eos_token_id), None
+    constraint, allowed_fn = constraints.normalize(kwargs, V, eos, batch, n_return)
+    rt, sampled = route(kwargs, rules, V, config.eos_token_id, allowed_fn is not None or (constraint is not None and not constraint.device_route)), None
     if kwargs.get("do_sample", False) and sampling.device_route(kwargs, V, config.eos_token_id):
         # seed=<int>: the draw moves into the captured graphs (device data, in no graph key).  Validated whatever the route: processors past the device caps still send it to the host loop
         sampled = sampling.normalize_params(kwargs.get("temperature"), kwargs.get("top_k"), kwargs.get("top_p")) + (int(kwargs["seed"]), int(kwargs.get("sample_row_base", 0) or 0))
@@ -118,7 +123,7 @@ def parse(kwargs, config, sync_every=None) -> Request:
                    generator=kwargs.get("generator"), want_dict=want_dict, want_scores=want_dict and bool(kwargs.get("output_scores")), want_logits=want_dict and bool(kwargs.get("output_logits")),
                    sync_every=sync_every if kwargs.get("sync_every") is None else int(kwargs["sync_every"]), forced=forced, attention_mask=kwargs.get("attention_mask"),
                    image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"), n_return=n_return,
-                   stops=stops, criteria=criteria, streamer=streamer)
+                   stops=stops, criteria=criteria, streamer=streamer, constraint=constraint, allowed_fn=allowed_fn)
 
 
 def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=None):
@@ -130,8 +135,13 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
     every callable is called once per step as c(ids [B, t], scores [B, V]) -- the tokens emitted in this call, this step's included, as HF calls a criterion when
     driven by inputs_embeds, and the step's processed logits -- and returns a bool (every row) or a bool tensor [B].  req.streamer: put(an empty [B, 0] tensor)
     first, put(tokens [B] on the CPU) after every pick, end() once.  finish: a list that receives one int64 [B] tensor, the column at which each row finished
-    (the number of tokens where it did not)."""
+    (the number of tokens where it did not).
+    req.constraint (constraints.Table): every row keeps a state; behind the logits processors and in front of the temperature, constraints.apply leaves only the
+    tokens with an edge out of the row's state, and the row's token -- pad for a finished row, as the device appends it -- then moves the state
+    (constraints.advance).  req.allowed_fn (prefix_allowed_tokens_fn=): at the same place, every unfinished row is masked to fn(b, the row's tokens emitted in
+    this call, an int64 1-D tensor)."""
     B, eos = logits.shape[0], list(req.eos)
+    states = None if req.constraint is None else req.constraint.starts(B // req.constraint.n_return)
     finished = torch.zeros(B, dtype=torch.bool, device=logits.device)
     finish_col = torch.full((B,), max_new, dtype=torch.int64, device=logits.device)
     toks, scores, raw = [], [], []
@@ -143,6 +153,11 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
             raw.append(z.clone())
         if req.rules.on:
             z = req.rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
+        if states is not None:
+            z = constraints.apply_rows(req.constraint, z, states)
+        elif req.allowed_fn is not None:
+            ids, done = torch.stack(toks, dim=1) if toks else torch.zeros((B, 0), dtype=torch.int64, device=z.device), finished.tolist()
+            z = torch.stack([z[b].float().clone() if done[b] else constraints.mask_to(z[b], req.allowed_fn(b, ids[b])) for b in range(B)])
         z = z / req.temperature  # (a new tensor; / 1.0 is exact)
         if step < req.min_new and eos:
             z[:, eos] = float("-inf")
@@ -158,6 +173,8 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
         nxt = z.argmax(dim=-1) if greedy else torch.multinomial(z.softmax(dim=-1), 1, generator=req.generator)[:, 0]
         nxt = torch.where(finished, torch.full_like(nxt, req.pad), nxt)
         toks.append(nxt)
+        if states is not None:
+            states = [constraints.advance(req.constraint, s, t) for s, t in zip(states, nxt.tolist())]
         if req.streamer is not None:
             req.streamer.put(nxt.detach().to("cpu", torch.int64))
         was = finished

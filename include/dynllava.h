@@ -498,6 +498,36 @@ int dl_logits_process(const void* logits, int logits_dtype, int64_t logits_row_s
                       float* out, const int64_t* out_ids, int out_cap, const int32_t* step,
                       const dl_logits_params* params, const int32_t* bad_words, void* stream);
 
+/* ---- constrained decoding (generate(constraint= / guided_choice= / allowed_token_ids=)): a deterministic token automaton walked on the device, one
+ * launch per step behind dl_logits_process (HF's order: PrefixConstrainedLogitsProcessor follows the repetition penalty, n-gram and bad-word processors) and
+ * in front of dl_decode_advance / dl_decode_sample, which take `out` (DL_F32) in place of the step's logits.
+ * The rule, per row (dynamic_llava_amd/constraints.py states it in full and is what the kernel is tested against), with s = clamp(step[b], 0, out_cap)
+ * (0 when step or out_ids is NULL):
+ *   1. the state: s == 0: start[b]; else prev = state_hist[b, s - 1], t = out_ids[b, s - 1]: the `next` of prev's edge with token t.  prev == DONE, no
+ *      such edge, or t outside [0, V): DONE.  A state outside [0, n_states), or whose edge range is not inside [0, n_edges], is DONE as well.
+ *   2. state_hist[b, s] = the state (slot j: the state in which token j is chosen); no other slot is written.
+ *   3. DONE: out_v = float32(logit_v) for every v.  Otherwise out_v = float32(logit_v) where the state has an edge with token v, -inf elsewhere.
+ * The table is DEVICE memory (one captured graph serves every automaton; the host rewrites it between requests): state s owns
+ * edges[state_ptr[s] : state_ptr[s + 1]], sorted by token, tokens distinct; next == DONE is the edge an EOS id takes out of an accepting state.  Nothing of
+ * the table is trusted: n_states / n_edges past the caps make every row DONE, every state_ptr value and every `next` is checked before it is used, an edge's
+ * token is used as an index only after it has been compared with the workgroup's range.  Words past state_ptr[n_states] and edges[n_edges] are never read.
+ * logits: bf16 / fp16 / fp32, any row stride; out: float [B, V], contiguous -- it MAY be `logits` itself (fp32, row stride V): every element is read and
+ * written by the same thread.  out_ids: int64 [B, out_cap]; step, start: int32 [B]; state_hist: int32 [B, out_cap + 1].  No workspace, no global atomics,
+ * never synchronises: capturable.  DL_ERR_ARG for a bad dtype, V < 1, B < 1 (or > 65535), a NULL logits / out / table / start / state_hist. */
+#define DL_CONSTRAIN_MAX_STATES 4096
+#define DL_CONSTRAIN_MAX_EDGES 131072
+#define DL_CONSTRAIN_DONE (-1)
+typedef struct dl_constraint_table {
+  int32_t n_states;
+  int32_t n_edges;
+  int32_t reserved[6];
+  int32_t state_ptr[DL_CONSTRAIN_MAX_STATES + 1];
+  int32_t edges[DL_CONSTRAIN_MAX_EDGES][2]; /* (token, next state) */
+} dl_constraint_table;
+int dl_logits_constrain(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int B,
+                        float* out, const int64_t* out_ids, int out_cap, const int32_t* step,
+                        const dl_constraint_table* table, const int32_t* start, int32_t* state_hist, void* stream);
+
 /* ---- log-probabilities of the tokens a generation picks (generate(output_logprobs=True, top_logprobs=n)): runs AFTER the step-closing launch
  * (dl_decode_advance / dl_decode_sample) on the step's RAW logits -- the model's own distribution, before logits processors, the min_new_tokens EOS ban and
  * temperature / top-k / top-p.  Per row b, with slot = step[b] - 1 (the slot the step-closing launch has just filled) and tok = next_ids[b] (the token it
