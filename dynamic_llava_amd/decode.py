@@ -26,12 +26,13 @@ class StepMode:
     logprobs: int = -1  # dl_decode_logprobs behind the kernel: generate(output_logprobs=True, top_logprobs=n) -- -1: off, else n
     stop: bool = False  # dl_decode_stop as the last launch: generate(stop_sequences= / stopping_criteria=[keyword criterion]); the list itself is device data
     constrained: bool = False  # dl_logits_constrain in front of the kernel: generate(constraint= / guided_choice= / allowed_token_ids=); the automaton itself is device data
+    guided: bool = False  # dl_logits_guide in front of everything, dl_pair_follow behind the kernel: generate(guidance_scale=) on paired rows; scale and cutoff are device data
 
     @classmethod
     def of(cls, req, max_new):
         """The mode of a parsed request (request.Request) of max_new steps; the one place the EOS tuple becomes the kernels' -1 / id / tuple."""
         return cls(eos=-1 if not req.eos else (req.eos[0] if len(req.eos) == 1 else req.eos), pad=req.pad, min_new=min(req.min_new, max_new), sampled=req.sampled is not None,
-                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp, stop=bool(req.stops), constrained=req.constraint is not None)
+                   forced=req.forced is not None, processed=req.rules.on, logprobs=req.n_lp, stop=bool(req.stops), constrained=req.constraint is not None, guided=req.guidance is not None)
 
 
 class _DecodeState:
@@ -114,6 +115,9 @@ class _DecodeState:
         # dl_logits_constrain's automaton, start states and state history (generate(constraint= / guided_choice= / allowed_token_ids=)): made by need_constraint() on
         # the first such request and with the state thereafter; rewritten by generate() before the first launch of a constrained request -- one graph serves every automaton
         self.con_table = self.con_start = self.con_hist = None
+        # dl_logits_guide's output and parameter block (generate(guidance_scale=): rows [0, B / 2) the prompts, row B / 2 + b prompt b's negative): made by
+        # need_guidance() on the first such request and with the state thereafter; the block is rewritten before the first launch of a guided request
+        self.guide_logits = self.guide_params = None
         self.tok_host = None  # generate(streamer=): ring of pinned token words beside obs_host, made by need_stream() on the first such request
         # dl_gemv_gu_tp's granules (batch 1; the predictor's stage 1 stages the row in LDS: H <= 5120)
         tpm = getattr(model.model, "output_text_score_predictor", None)
@@ -154,6 +158,12 @@ class _DecodeState:
             self.con_table = ops.constraint_table_block(dev)
             self.con_start = torch.full((B,), -1, dtype=torch.int32, device=dev)
             self.con_hist = torch.full((B, cap + 1), -1, dtype=torch.int32, device=dev)  # slot j: the state in which token j is chosen
+
+    def need_guidance(self):
+        """Allocates dl_logits_guide's fp32 [B, V] output and its parameter block once per state (the captured launches hold their pointers)."""
+        if self.guide_logits is None:
+            self.guide_logits = torch.empty(self.logits.shape, dtype=torch.float32, device=self.logits.device)
+            self.guide_params = ops.guide_params_block(self.logits.device)
 
     def need_stream(self, chunk):
         """The pinned ring the chunks' tokens leave through (generate(streamer=)): 4 slots of B x chunk int64 words, one per observation in flight."""
@@ -213,10 +223,14 @@ class DecodeScheduler:
         lf, ls = (None, None) if cache is None else (cache.len_full, cache.len_sparse)
         dec = st.decision if cache is not None and self._use_tp() else None
         logits, m = st.logits, self._mode
+        if m.guided:  # generate(guidance_scale=): HF's first processor -- both rows of a pair get the pair's guided scores (fp32, a buffer of its own); st.logits is never written
+            if m.forced:
+                raise ValueError("score() takes no guidance: a label is scored on the model's own logits")
+            logits = ops.logits_guide(st.logits, st.guide_logits, st.guide_params)
         if m.processed:  # generate() with logits processors: they edit the step's logits on the row's own history (HF's order: before the selection rule)
             if m.forced:
                 raise ValueError("score() takes no logits processors: a label is scored on the model's own logits")
-            logits = ops.logits_process(st.logits, st.proc_logits, st.logits_params, st.out_ids, st.step, st.bad_words)
+            logits = ops.logits_process(logits, st.proc_logits, st.logits_params, st.out_ids, st.step, st.bad_words)
         if m.constrained:  # generate() with a constraint: behind the processors (HF's order), every token without an edge out of the row's state becomes -inf; st.logits is never written
             if m.forced:
                 raise ValueError("score() takes no constraint: a label is scored on the model's own logits")
@@ -227,6 +241,8 @@ class DecodeScheduler:
             ops.decode_sample(logits, st.cur_ids, st.sample_params, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
         else:  # EOS is banned while step < min_new (HF semantics)
             ops.decode_advance(logits, st.cur_ids, st.out_ids, st.step, st.finished, m.eos, m.pad, lf, ls, dec, min_new_tokens=m.min_new)
+        if m.guided:  # the negative row follows its prompt's row (token, out_ids slot, finished flag): one history per pair, also when the two rows drew from two random streams
+            ops.pair_follow(st.cur_ids, st.out_ids, st.step, st.finished)
         if m.logprobs >= 0:  # generate(output_logprobs=True): the committed token's log-probability on the step's RAW logits (slot step - 1)
             ops.decode_logprobs(st.logits, st.cur_ids, st.step, st.lp, m.logprobs, st.top_lp, st.top_ids)
         if m.stop:  # generate(stop_sequences=): a row whose tokens now end in a stop sequence is finished, as by an EOS token -- the last launch, so all above see today's flags
@@ -506,6 +522,21 @@ class DecodeScheduler:
         cache.set_bounds(None, None)
         cache.sched_begin(max(cache.full_len_host), cache.prefill_sparse_max, self.decode_sync_every)
 
+    def _place_host_mirrors(self, src, cache, row0, close):
+        """The host mirrors of the 2 B-row cache of a guided request behind one of its two dl_kv_place launches: rows row0 .. take what _prefill_host_update left on the
+        source; the bounds that hold for every row are the looser of the two prefills' (a text-only negative drops no image tokens).  close: the second one."""
+        B = src.batch
+        cache.full_len_host[row0 : row0 + B] = list(src.full_len_host)
+        drop = src.logical_cap - src.sparse_cap
+        first = row0 == 0
+        cache.seen_tokens = src.seen_tokens if first else max(cache.seen_tokens, src.seen_tokens)
+        cache._place_drop = drop if first else min(cache._place_drop, drop)
+        cache.prefill_sparse_max = src.prefill_sparse_max if first else max(cache.prefill_sparse_max, src.prefill_sparse_max)
+        if close:
+            cache.sparse_cap = cache.logical_cap - cache._place_drop
+            cache.set_bounds(None, None)
+            cache.sched_begin(max(cache.full_len_host), cache.prefill_sparse_max, self.decode_sync_every)
+
     def _drop_graphs_on(self, ptr):
         """Forget every captured prefill and decode step whose key holds the slab pointer `ptr`: the slab was freed, or handed to a caller who may free it."""
         self._prefill_graphs = {k: v for k, v in self._prefill_graphs.items() if ptr not in k}
@@ -532,8 +563,12 @@ class DecodeScheduler:
         if req.constraint is not None:
             st.need_constraint()
             ops.constraint_table_write(st.con_table, *req.constraint.words())
-            st.con_start.copy_(torch.tensor(req.constraint.starts(st.B // req.constraint.n_return), dtype=torch.int32))
+            pairs = 2 if req.guidance is not None else 1  # (a guided request: row B + b walks prompt b's automaton beside row b)
+            st.con_start.copy_(torch.tensor(req.constraint.starts(st.B // (req.constraint.n_return * pairs)) * pairs, dtype=torch.int32))
             st.con_hist.fill_(-1)  # DONE: a slot no launch of this request reaches shows no earlier request's state
+        if req.guidance is not None:
+            st.need_guidance()
+            st.guide_params.copy_(ops.guide_params_words(*req.guidance))
         if req.forced is not None:
             st.labels.fill_(IGNORE_INDEX)
             st.labels[:, : req.forced.shape[1]].copy_(req.forced)
@@ -617,11 +652,14 @@ class DecodeScheduler:
         for _ in range(n_steps):
             g.replay()
 
-    def _first_token(self, st, x_last, fork=None):
+    def _first_token(self, st, x_last, fork=None, place=None):
         """fork = (source cache, cache, n, host bound of the prompt lengths): generate(num_return_sequences=n) -- x_last holds the B prompts' last rows; their logits are computed at B rows, on the route a
-        plain call of B rows takes (the same bits), the prompts' K/V is forked into the B * n-row cache and every logits row repeated n times in front of the bookkeeping."""
+        plain call of B rows takes (the same bits), the prompts' K/V is forked into the B * n-row cache and every logits row repeated n times in front of the bookkeeping.
+        place: (source cache, cache, maps, row0, close, host bound of the prompt lengths): one of the two prefills of a guided request (generate(guidance_scale=)) -- x_last holds
+        B rows' last rows, prompts (row0 = 0) or negative prompts (row0 = B); their logits are computed at B rows as above, dl_kv_place puts their K/V into rows row0 .. of the
+        2 B-row cache and the logits go to the same rows of st.logits; only the closing one (the negatives') runs the first token's bookkeeping, on all 2 B rows."""
         logits, use_gemv = st.logits, st.use_gemv
-        if fork is not None:
+        if fork is not None or place is not None:
             cfg, logits = self.config, self._fork_logits
             use_gemv = logits.shape[0] <= min(self.gemv_max_decode_batch, ops.gemv_max_batch(cfg.intermediate_size, self.dtype), ops.gemv_max_batch(cfg.hidden_size, self.dtype))  # _DecodeState.use_gemv at B rows
         if use_gemv and x_last.dim() == 2 and x_last.is_contiguous():
@@ -633,6 +671,12 @@ class DecodeScheduler:
             src, cache, n, max_len = fork
             ops.kv_fork(src, cache, n, max_len=max_len)  # (the prompts' lengths are read on the device; max_len, the longest row the plan allows, sizes the grid)
             st.logits.view(logits.shape[0], n, -1).copy_(logits[:, None, :].expand(-1, n, -1))
+        if place is not None:
+            src, cache, maps, row0, close, max_len = place
+            ops.kv_place(src, cache, *maps, max_len=max_len)
+            st.logits[row0 : row0 + logits.shape[0]].copy_(logits)
+            if not close:
+                return
         self._prefill_logits_buf.copy_(st.logits)
         self._bookkeep(st, None)  # first token: the prompt's KV lengths are already in place; label 0 is scored on / token 0 drawn (step = 0) from the prompt's last logits
 
@@ -661,7 +705,7 @@ class DecodeScheduler:
                 st.obs_ev[slot].synchronize()
                 row = st.obs_host[slot]
                 if feed is not None:
-                    feed.push(st.tok_host[slot, : B * n_tok].view(B, n_tok).clone())
+                    feed.push(st.tok_host[slot, : B * n_tok].view(B, n_tok)[: feed.seen.shape[0]].clone())  # (a guided request: the prompts' rows, the first half)
                 cache.sched_observe(at, int(row[B : 2 * B].max()))
                 all_done = all_done or (stops and int(row[2 * B :].min()) != 0)
             if all_done:

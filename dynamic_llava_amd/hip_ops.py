@@ -175,6 +175,10 @@ SIGNATURES = {
     "dl_logits_constrain": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dl_decode_logprobs": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dl_decode_stop": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dl_kv_place": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_int,
+                            c_int, c_int, c_void_p, c_int64, c_void_p, c_int64, c_int, c_void_p]),
+    "dl_logits_guide": (c_int, [c_void_p, c_int, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dl_pair_follow": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib = None
@@ -1477,6 +1481,91 @@ def kv_fork(src_cache, dst_cache, n_rep, max_len=None):
     kv_fork_arrays(s.slab, d.slab, s.sparse_layer, n_rep, s.lens, d.lens, max_len)
     if s.kv_format == "mxfp8":
         kv_fork_arrays(s.scales, d.scales, s.sparse_layer, n_rep, s.lens, None, max_len)
+
+
+def kv_place_maps(src_rows, dst_rows, B_src, B_dst, device):
+    """The row maps of dl_kv_place, checked on the host and put on the device (outside any capture): equally many source and destination rows, every one
+    inside its cache, the destination rows distinct -> (src_rows, dst_rows) int32 DEVICE tensors."""
+    s, d = [int(v) for v in src_rows], [int(v) for v in dst_rows]
+    if not s or len(s) != len(d) or any(not 0 <= v < B_src for v in s) or any(not 0 <= v < B_dst for v in d) or len(set(d)) != len(d):
+        raise HipOpsError(f"kv_place_maps: source rows {s} of a cache of {B_src} rows -> destination rows {d} of one of {B_dst} rows is no valid map "
+                          "(equally many, inside their caches, destination rows distinct)")
+    return torch.tensor(s, dtype=torch.int32, device=device), torch.tensor(d, dtype=torch.int32, device=device)
+
+
+def kv_place_arrays(src, dst, sparse_layer, src_rows, dst_rows, src_lens, dst_lens=None, max_len=None):
+    """dl_kv_place on one storage array (include/dynllava.h).  src [L, 2, B_src, nKV, T_src, w] and dst [L, 2, B_dst, nKV, T_dst, w] of one element type, the last
+    two dimensions dense; src_rows / dst_rows int32 [n] DEVICE tensors (kv_place_maps); src_lens int32 [2, B_src] (dst_lens [2, B_dst], optional): read / written
+    on the device.  max_len: host bound of the lengths (default: the smaller capacity)."""
+    _dev(src, dst, src_lens, dst_lens, src_rows, dst_rows)
+    assert src.dim() == 6 and dst.dim() == 6 and src.dtype == dst.dtype and src.shape[1] == 2 and dst.shape[1] == 2
+    L, _, B_src, nKV, T_src, w = src.shape
+    B_dst, T_dst, es = dst.shape[2], dst.shape[4], src.element_size()
+    assert tuple(dst.shape) == (L, 2, B_dst, nKV, T_dst, w), (tuple(src.shape), tuple(dst.shape))
+    for t in (src, dst):
+        assert t.stride(5) == 1 and t.stride(4) == w
+    for r in (src_rows, dst_rows):
+        assert r.dtype == torch.int32 and r.dim() == 1 and r.is_contiguous() and r.numel() == src_rows.numel() >= 1
+    assert src_lens.dtype == torch.int32 and tuple(src_lens.shape) == (2, B_src) and src_lens.stride(1) == 1
+    assert dst_lens is None or (dst_lens.dtype == torch.int32 and tuple(dst_lens.shape) == (2, B_dst) and dst_lens.stride(1) == 1)
+    _check(
+        lib().dl_kv_place(_p(src), _p(dst), *(src.stride(i) * es for i in range(4)), *(dst.stride(i) * es for i in range(4)), L, int(sparse_layer), B_src, B_dst,
+                          int(src_rows.numel()), _p(src_rows), _p(dst_rows), nKV, w * es, T_src, T_dst, _p(src_lens), src_lens.stride(0), _p(dst_lens),
+                          0 if dst_lens is None else dst_lens.stride(0), min(T_src, T_dst) if max_len is None else int(max_len), _stream()),
+        "dl_kv_place",
+    )
+
+
+def kv_place(src_cache, dst_cache, src_rows, dst_rows, max_len=None):
+    """Place rows of a KV cache into rows of another (cache.KVSlabCache or KVSlabCacheMX8, both of one format and shape but for the batch): source row
+    src_rows[i]'s live slots and its two lengths go to destination row dst_rows[i] (int32 DEVICE tensors of kv_place_maps).  One launch per storage array
+    (the slab; with MXFP8 the scale bytes too); capturable."""
+    s, d = src_cache, dst_cache
+    if (s.kv_format, s.n_layers, s.sparse_layer, s.n_kv_heads, s.head_dim) != (d.kv_format, d.n_layers, d.sparse_layer, d.n_kv_heads, d.head_dim):
+        raise HipOpsError("kv_place: the two caches differ in format / shape")
+    kv_place_arrays(s.slab, d.slab, s.sparse_layer, src_rows, dst_rows, s.lens, d.lens, max_len)
+    if s.kv_format == "mxfp8":
+        kv_place_arrays(s.scales, d.scales, s.sparse_layer, src_rows, dst_rows, s.lens, None, max_len)
+
+
+def guide_params_words(scale=1.0, cutoff=None):
+    """dl_guide_params (include/dynllava.h) as a CPU int32 [8] tensor: copy it into the device block (`guide_params_block`) before the first launch of a request.
+    cutoff: None (off) or beta in (0, 1); log(beta) is rounded to fp32 here, on the host (guidance.log_beta)."""
+    import struct
+
+    from .guidance import log_beta
+
+    raw = struct.pack("<fifiiiii", float(scale), 0 if cutoff is None else 1, 0.0 if cutoff is None else log_beta(cutoff), 0, 0, 0, 0, 0)
+    return torch.frombuffer(bytearray(raw), dtype=torch.int32).clone()
+
+
+def guide_params_block(device):
+    """Device memory for one dl_guide_params (write it with `block.copy_(guide_params_words(...))`)."""
+    return guide_params_words().to(device)
+
+
+def logits_guide(logits, out, params):
+    """Classifier-free guidance of one step (include/dynllava.h, guidance.py): logits [2 * P, V] (any row stride; rows [0, P) conditional, row P + p pair p's
+    negative) -> out fp32 [2 * P, V], contiguous, both rows of a pair the same guided scores.  params: int32 [8] DEVICE tensor holding a dl_guide_params."""
+    _dev(logits, out, params)
+    assert logits.dim() == 2 and logits.stride(1) == 1 and logits.shape[0] % 2 == 0 and logits.shape[0] >= 2
+    B2, V = logits.shape
+    assert out.dtype == torch.float32 and out.shape == (B2, V) and out.is_contiguous() and out.data_ptr() != logits.data_ptr()
+    if params is not None:  # (None reaches the library, which refuses it)
+        assert params.dtype == torch.int32 and params.numel() >= 8 and params.is_contiguous()
+    _check(lib().dl_logits_guide(_p(logits), dtype_code(logits.dtype), logits.stride(0), V, B2 // 2, _p(out), _p(params), _stream()), "dl_logits_guide")
+    return out
+
+
+def pair_follow(next_ids, out_ids, step, finished):
+    """Behind the step-closing launch of a guided step (include/dynllava.h): row P + p takes row p's next_ids, its out_ids slot step[p] - 1 and its finished
+    flag.  next_ids int64 [2 * P]; out_ids int64 [2 * P, cap]; step, finished int32 [2 * P]."""
+    _dev(next_ids, out_ids, step, finished)
+    assert out_ids.dtype == torch.int64 and out_ids.dim() == 2 and out_ids.is_contiguous() and out_ids.shape[0] % 2 == 0 and out_ids.shape[0] >= 2
+    B2, cap = out_ids.shape
+    assert next_ids.dtype == torch.int64 and next_ids.numel() == B2 and next_ids.is_contiguous()
+    assert step.dtype == torch.int32 and step.numel() == B2 and step.is_contiguous() and finished.dtype == torch.int32 and finished.numel() == B2 and finished.is_contiguous()
+    _check(lib().dl_pair_follow(B2 // 2, _p(next_ids), _p(out_ids), int(cap), _p(step), _p(finished), _stream()), "dl_pair_follow")
 
 
 def prompt_layout(input_ids, n_feat, image_token, user_ids):

@@ -21,6 +21,7 @@ Design (not a translation of the reference's op sequence):
 """
 from __future__ import annotations
 
+import copy
 import dataclasses
 import operator
 import os
@@ -30,7 +31,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 from . import hip_ops as ops
-from . import constraints, logprobs, request, sampling, scoring, stopping
+from . import constraints, guidance, logprobs, request, sampling, scoring, stopping
 from .cache import KVSlabCache
 from .config import IGNORE_INDEX, IMAGE_TOKEN_INDEX, DynamicLlavaConfig
 
@@ -547,13 +548,22 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         max_new = req.max_new(cache.full_len_host)
         # last VALID position of every row: the logits are right-padded with zeros when rows differ in length; the last layer's KV length is the (compacted) row length
         last = cache[1][-1].to(self.device).long() - 1
-        return self._host_decode(req, cache, out.logits[torch.arange(out.logits.shape[0], device=self.device), last].float(), max_new, greedy)
+        last_logits = lambda o, at: o.logits[torch.arange(o.logits.shape[0], device=self.device), at].float()
+        neg = None
+        if req.guidance is not None:  # the negative prompts: a second stream on a cache of its own, advanced with the same picked tokens (request.host_loop)
+            n_ids, n_mask, n_images, n_feats = guidance.negative_inputs(kwargs, inputs, images, IMAGE_TOKEN_INDEX)
+            n_out = self.forward(n_ids.to(self.device), attention_mask=n_mask, images=n_images, image_features=n_feats)
+            neg = (last_logits(n_out, n_out.past_key_values[1][-1].to(self.device).long() - 1), n_out.past_key_values)
+        return self._host_decode(req, cache, last_logits(out, last), max_new, greedy, neg)
 
-    def _host_decode(self, req, cache, logits, max_new, greedy):
-        """A host route behind its first forward(): request.host_loop over single decode steps on `cache` -> the tokens [B, T_new], or generate()'s dict."""
+    def _host_decode(self, req, cache, logits, max_new, greedy, neg=None):
+        """A host route behind its first forward(): request.host_loop over single decode steps on `cache` -> the tokens [B, T_new], or generate()'s dict.
+        neg = (the negative stream's first logits, its cache): a guided request."""
         self.last_prefill_logits = logits.clone()
         finish = []  # the rows' finish columns, asked for only where a row can finish on more than EOS
         more = dict(finish=finish) if (req.stops or req.criteria) else {}
+        if neg is not None:
+            more["negative"] = (neg[0], lambda nxt: self.forward(nxt[:, None], past_key_values=neg[1]).logits[:, -1].float())
         toks, scores, raw = request.host_loop(logits, lambda nxt: self.forward(nxt[:, None], past_key_values=cache).logits[:, -1].float(), req, max_new, greedy, **more)
         seq, self.last_cache = torch.stack(toks, dim=1), cache
         if not req.want_dict:
@@ -615,6 +625,8 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         output_logits=True adds logits: a tuple of fp32 [B, V], one per step (the step-by-step route of generate(output_logits=True), for tests)."""
         if any(k in constraints.KEYWORDS for k in kwargs):  # (constrained decoding restricts what a row may say; a label sequence is scored as it stands)
             raise ValueError(f"score() takes no constraint ({', '.join(k for k in kwargs if k in constraints.KEYWORDS)}): a label is scored on the model's own logits")
+        if any(k in guidance.KEYWORDS for k in kwargs):  # (guidance changes which token is picked; a label sequence is scored as it stands)
+            raise ValueError(f"score() takes no guidance ({', '.join(k for k in kwargs if k in guidance.KEYWORDS)}): a label is scored on the model's own logits")
         if kwargs:
             raise TypeError(f"score() got an unexpected keyword argument {next(iter(kwargs))!r}")
         if not torch.is_tensor(input_ids) or input_ids.dim() != 2:
@@ -684,6 +696,19 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         [rows]: the row ended through an EOS edge instead of being cut off by max_new_tokens.  A dead end, an EOS id that is an edge of an accepting state,
         min_new_tokens > 0, two of the keywords, or any of them in score() raise ValueError before any launch; a row that processors and constraint together leave all
         -inf is the caller's error, as in HF.
+        guidance_scale=s (a finite float >= 0; None and 1.0 are the request without the keyword) with negative_prompt_ids= (int64 [B, Wn] or [1, Wn], laid out as
+        `inputs` are: a row with the <image> placeholder takes an image, a row without it is text-only) and / or negative_images= (the images of the negative rows
+        that hold a placeholder, default the request's; without negative_prompt_ids the negative ids are `inputs`: same text, another image), negative_prompt_attention_mask=
+        (belongs to negative_prompt_ids), guidance_cutoff=beta in (0, 1): classifier-free guidance / visual contrastive decoding.  Every step's scores are
+        s * (logprob_cond - logprob_neg) + logprob_neg, with beta only where logprob_cond >= max logprob_cond + log(beta) (-inf elsewhere) -- HF's
+        UnbatchedClassifierFreeGuidanceLogitsProcessor, in HF's place: in front of the logits processors, the constraint, the EOS ban, temperature, top-k and top-p (the
+        rule is guidance.py).  On the device the negative prompt is a second ROW of the same captured decode step: state and cache have 2 B rows (row B + b is prompt
+        b's negative), prompts and negatives are prefilled as two batches of B and placed by dl_kv_place, dl_logits_guide writes the guided scores of a pair to both
+        its rows in front of the other logits launches, dl_pair_follow keeps the negative row on its prompt's tokens; scale and cutoff are device data, one graph
+        serves every setting.  Every per-row result is the B prompts'; with output_logits=True the dict also has `negative_logits` (the negative rows' raw logits per
+        step), and the returned cache is an independent B-row copy of the prompts' rows.  `logits` and the log-probabilities stay the conditional rows' own.  The host
+        routes run two streams on two caches with the same rule.  A bad scale or cutoff, an active scale without negative_prompt_ids / negative_images, a cutoff without
+        an active scale, or any of these keywords in score() raise ValueError; with num_return_sequences > 1 or past_key_values NotImplementedError; before any launch.
         Still ignored without a word: logits_processor, suppress_tokens, sequence_bias.
         Steady state (same prompt SHAPE as a previous call): the whole prefill -- CLIP, projector, embedding assembly,
         32 layers, first-token argmax -- is one hipGraph replay and every decode step is another; the host only copies
@@ -707,48 +732,90 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
         # K/V into n rows of the B * n-row cache and the first-step logits are repeated, so the n rows of a prompt draw n first tokens (row b * n + r: Philox counter row
         # row_base + b * n + r).  Everything behind the prefill serves a B * n-row state as it serves any batch
         n = req.n_return
-        cache = self._pooled_cache(B * n, max(lens) + max_new + 1)
+        # guidance_scale (active): the pair layout -- decode state and cache have 2 B rows, rows [0, B) the prompts, row B + b prompt b's negative; prompts and negatives are
+        # prefilled as two batches of B, each exactly as a plain call of them would be, into the pooled source cache and from there (dl_kv_place) into their rows; every
+        # per-row result of the call is rows [:B]
+        neg = None if req.guidance is None else self._guided_negatives(kwargs, inputs, images, req)
+        rows, longest = B * n * (1 if neg is None else 2), max(lens if neg is None else lens + neg["lay"]["lens"])
+        cache = self._pooled_cache(rows, longest + max_new + 1)
         fork = None if n == 1 else (self._fork_source(B, max(lens) + 1), n)
-        self._rope_tables(max(lens) + max_new + 1)
-        st = self._get_dstate(B * n, max_new)
+        self._rope_tables(longest + max_new + 1)
+        st = self._get_dstate(rows, max_new)
         self._bind_schedule(st, cache)
         self._arm(st, req, max_new)
-        ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new, fork)
-        self.last_prefill_logits = self._prefill_logits_buf
+        ents = []
+        if neg is None:
+            ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new, fork)
+            ents.append((ent, dev_layout))
+        else:
+            maps = self._pair_maps(B)
+            ent, prefill_path = self._generate_prefill(lay, dev_layout, inputs, images, req.image_features, cache, st, max_new, place=(self._fork_source(B, longest + 1), maps[0], 0, False))
+            nent, _ = self._generate_prefill(neg["lay"], neg["dev"], neg["ids"], neg["images"], neg["feats"], cache, st, max_new, place=(self._fork_source(B, longest + 1), maps[1], B, True))
+            ents += [(ent, dev_layout), (nent, neg["dev"])]
+
+        def layout_failed():  # a device layout met a row without exactly one image token: what was computed is meaningless (the flag is read with the call's own synchronisation)
+            bad = [e for e, d in ents if d and int(e["didx"]["err"].item()) != 0]
+            for e in bad:
+                e["didx"]["err"].zero_()
+            return bool(bad)
+
+        self.last_prefill_logits = self._prefill_logits_buf if neg is None else self._prefill_logits_buf[:B]  # (a guided request: the prompts' rows, like every per-row result)
         if tm is not None:
             tm["ev"][1].record()
             tm["path"] = prefill_path
-        scores, raw_logits = [], []
-        on_step = (lambda j: self._score(req, st, j, scores, raw_logits)) if (req.want_scores or req.want_logits) else None
+        scores, raw_logits, neg_logits = [], [], []
+        on_step = (lambda j: self._score(req, st, j, scores, raw_logits, neg_logits)) if (req.want_scores or req.want_logits) else None
         if on_step is not None:
             on_step(0)
         feed = None
         if req.streamer is not None:
-            if dev_layout and int(ent["didx"]["err"].item()) != 0:  # (the check below, made before a token of a meaningless run reaches the streamer)
-                ent["didx"]["err"].zero_()
+            if layout_failed():  # (the check below, made before a token of a meaningless run reaches the streamer)
                 return self.generate(inputs, images=images, image_sizes=image_sizes, _host_layout=True, **kwargs)
             feed = stopping.Feed(req.streamer, B * n, req.eos, req.stops)
-            feed.push(st.out_ids[:, :1].cpu())  # the first token: the caller waits for it
+            feed.push(st.out_ids[: B * n, :1].cpu())  # the first token: the caller waits for it
         produced = self._decode_loop(st, cache, max_new, req.sync_every, on_step, feed)
-        if B * n == 1 or self._lp_ws is not None:
+        if rows == 1 or self._lp_ws is not None:
             self.check_device_errors()  # (B > 1 too: dl_linear_packed's k ranges hand over in-kernel, through _lp_err; generate() is about to synchronise for its result anyway)
-        if dev_layout and int(ent["didx"]["err"].item()) != 0:
+        if layout_failed():
             # a row without exactly one image token (text-only row, several images): what was computed is meaningless -- repeat the
             # call with the host-side layout, which handles (or rejects) those rows like the reference does
-            ent["didx"]["err"].zero_()
             return self.generate(inputs, images=images, image_sizes=image_sizes, _host_layout=True, **kwargs)
-        res = self._finish(req, st, cache, produced, scores, raw_logits, tm)
+        res = self._finish(req, st, cache, produced, scores, raw_logits, tm, neg_logits)
         if feed is not None:
             feed.finish(res["sequences"] if isinstance(res, dict) else res)
         return res
 
-    def _score(self, req, st, step_idx, scores, raw_logits):
-        """The device route's per-step callback: appends HF's `scores` of the step (the processed logits, EOS at -inf while step < min_new_tokens) and the raw logits."""
+    def _guided_negatives(self, kwargs, inputs, images, req):
+        """The negative rows of a guided request, laid out as the prompts are -> dict(ids, images, feats, lay, dev)."""
+        ids, mask, n_images, n_feats = guidance.negative_inputs(kwargs, inputs, images, IMAGE_TOKEN_INDEX)
+        ids = ids.to(self.device)
+        lay, dev = self._generate_layout(ids, dataclasses.replace(req, attention_mask=mask, image_features=n_feats), self._n_feat(n_images, n_feats))
+        return dict(ids=ids, images=n_images, feats=n_feats, lay=lay, dev=dev)
+
+    def _pair_maps(self, B):
+        """dl_kv_place's row maps of a guided request of B pairs, on the device (made once: captured prefills hold their pointers): source rows 0 .. B - 1 -> the
+        prompts' rows 0 .. B - 1 (also the way back, into the caller's B-row cache) and -> the negatives' rows B .. 2 B - 1."""
+        maps = getattr(self, "_pair_maps_dev", None)
+        if maps is None:
+            maps = self._pair_maps_dev = {}
+        if B not in maps:
+            r = list(range(B))
+            maps[B] = (ops.kv_place_maps(r, r, B, 2 * B, self.device), ops.kv_place_maps(r, [B + b for b in r], B, 2 * B, self.device))
+        return maps[B]
+
+    def _score(self, req, st, step_idx, scores, raw_logits, neg_logits=None):
+        """The device route's per-step callback: appends HF's `scores` of the step (the processed logits, EOS at -inf while step < min_new_tokens) and the raw logits.
+        A guided request (rows [:P] the prompts, [P:] their negatives): all of rows [:P]; the negative rows' raw logits go to neg_logits."""
         z = (self._prefill_logits_buf if step_idx == 0 else st.logits).float().clone()
+        P = z.shape[0] // 2 if req.guidance is not None else z.shape[0]
         if req.want_logits:
-            raw_logits.append(z.clone())
+            raw_logits.append(z[:P].clone())
+            if req.guidance is not None:
+                neg_logits.append(z[P:].clone())
+        if req.guidance is not None:  # what dl_logits_guide left: both rows of a pair hold the pair's guided scores
+            z = st.guide_logits[:P].clone()
         if req.rules.on or req.constraint is not None:  # what dl_logits_process / dl_logits_constrain left for this step's bookkeeping launch
-            z = st.proc_logits.clone()
+            z = st.proc_logits[:P].clone()
         banned = list(req.eos) if step_idx < req.min_new else []
         if req.sampled is not None:  # z = logit / T with -inf outside the kept set, as HF reports a sampled step: on the host, with the contract's own arithmetic (sampling.py)
             z = sampling.processed_logits(z.cpu(), *req.sampled[:3], banned).to(z.device)
@@ -756,16 +823,18 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             z[:, banned] = float("-inf")
         scores.append(z)
 
-    def _finish(self, req, st, cache, produced, scores, raw_logits, tm):
-        """The device route's result: the host mirrors of what the loop advanced, the EOS trim, then the tokens, generate()'s dict or score()'s."""
+    def _finish(self, req, st, cache, produced, scores, raw_logits, tm, neg_logits=()):
+        """The device route's result: the host mirrors of what the loop advanced, the EOS trim, then the tokens, generate()'s dict or score()'s.  A guided request
+        (rows [:P] the prompts, [P:] their negatives) reports rows [:P], and its cache is an independent P-row copy of the conditional rows (dl_kv_place)."""
         cache.full_len_host = [n + produced - 1 for n in cache.full_len_host]  # every row's un-evicted length grows by one per decode step
         cache.seen_tokens += produced - 1
-        out, finish = st.out_ids[:, :produced].clone(), None
+        P = st.B // 2 if req.guidance is not None else st.B
+        out, finish = st.out_ids[:P, :produced].clone(), None
         if req.eos or req.stops:  # HF stops as soon as every row has finished (an EOS id, or a stop sequence's last token): trim the columns produced after that
             finish = stopping.finish_columns(out, req.eos, req.stops)
             first = int(finish.max().item())
             if first < out.shape[1]:
-                out, scores, raw_logits = out[:, : first + 1], scores[: first + 1], raw_logits[: first + 1]
+                out, scores, raw_logits, neg_logits = out[:, : first + 1], scores[: first + 1], raw_logits[: first + 1], neg_logits[: first + 1]
         self.last_cache = cache
         if tm is not None:
             tm["ev"][2].record()
@@ -778,16 +847,30 @@ class DynamicLlavaLlamaForCausalLM(PrefillEngine, DecodeScheduler, nn.Module):
             return out
         # the caller keeps this cache (the reference returns an independent one per call): detach it from the pool, the next generate() allocates a fresh
         # slab instead of overwriting this one; captured graphs hold raw pointers into the slab the caller now owns (and may free): drop them
-        self._cache_pool = None
-        self._drop_graphs_on(cache.slab.data_ptr())
+        if req.guidance is not None:  # the conditional rows, copied out: the 2 P-row slab and the graphs captured on it stay with the model
+            pairs = cache
+            cache = self._new_cache(P, pairs.t_cap)
+            ops.kv_place(pairs, cache, *self._pair_maps(P)[0], max_len=max(pairs.full_len_host[:P]))
+            cache.full_len_host, cache.seen_tokens = list(pairs.full_len_host[:P]), max(pairs.full_len_host[:P])
+            cache.logical_cap, cache.sparse_cap = pairs.logical_cap, pairs.sparse_cap
+            # ... and what a continuation under forward() schedules by, as the plain path's cache carries it: the pair cache's bounds hold for all 2 P rows, so for these P
+            cache.prefill_sparse_max = pairs.prefill_sparse_max
+            cache.set_bounds(pairs.full_bound, pairs.sparse_bound)
+            cache._sch = copy.deepcopy(pairs._sch)
+            self.last_cache = cache
+        else:
+            self._cache_pool = None
+            self._drop_graphs_on(cache.slab.data_ptr())
         res = {"sequences": out, "past_key_values": cache}
         if req.want_scores:
             res["scores"] = tuple(scores)
         if req.want_logits:
             res["logits"] = tuple(raw_logits)
+            if req.guidance is not None:
+                res["negative_logits"] = tuple(neg_logits)
         if req.n_lp >= 0:  # the columns `sequences` kept; after a row's first EOS (pad in `sequences`) 0.0 / -1
             W, n = out.shape[1], req.n_lp
-            lp, top_lp, top_ids = st.lp[:, :W].clone(), st.top_lp[:, :W, :n].clone(), st.top_ids[:, :W, :n].clone()
+            lp, top_lp, top_ids = st.lp[:P, :W].clone(), st.top_lp[:P, :W, :n].clone(), st.top_ids[:P, :W, :n].clone()
             if req.stops:  # (a row also finishes on a stop sequence: by its finish column)
                 logprobs.mask_after_columns(finish, lp, top_lp, top_ids)
             else:

@@ -571,21 +571,27 @@ class PrefillEngine:
         return dict(sig=("dev", Bq, Wb, n_feat), B=Bq, lens=[n_row] * Bq, lens_bucket=[n_row_b] * Bq, indices=fake, text_src=[0], text_dst=[0], img_dst=[0], img_rows=list(range(Bq)),
                     total=Bq * n_row_b, n_feat=n_feat, width=Wq, bucket=Wb), True
 
-    def _generate_prefill(self, lay, dev_layout, inputs, images, image_features, cache, st, max_new, fork=None):
+    def _generate_prefill(self, lay, dev_layout, inputs, images, image_features, cache, st, max_new, fork=None, place=None):
         """generate()'s prefill, the first token's bookkeeping launch included -> (entry of _prefill_graphs, path: "eager" on a shape's first sighting, then
         "graph-capture", then "graph-replay"); a model that cannot be captured (use_hip_graph off, debug_records, hooks) keeps no entry: (None, "eager").
         fork = (source cache, n) (num_return_sequences = n > 1): the prompts are prefilled into the source cache, at their own batch, and forked into `cache`'s B * n rows
-        in front of the first token's launch (_first_token) -- inside the same closure, so inside the captured graph."""
+        in front of the first token's launch (_first_token) -- inside the same closure, so inside the captured graph.
+        place = (source cache, (src_rows, dst_rows) of ops.kv_place_maps, row0, close) (generate(guidance_scale=)): one of the two prefills of a guided request -- B rows, prompts
+        or negative prompts, prefilled into the source cache exactly as a plain call of them would be, then placed into rows row0 .. row0 + B - 1 of `cache`'s 2 B rows by
+        dl_kv_place, inside the same closure; only the closing one runs the first token's launches (_first_token)."""
         lens, indices, B, n_feat = lay["lens"], lay["indices"], lay["B"], lay["n_feat"] if dev_layout else None
-        target = cache if fork is None else fork[0]  # the cache the prefill writes
+        target = fork[0] if fork is not None else (place[0] if place is not None else cache)  # the cache the prefill writes
+        placed = lambda max_len: None if place is None else (target, cache, place[1], place[2], place[3], max_len)
         vp = getattr(self.model, "image_score_predictor", None)
         if not (self.use_hip_graph and self.debug_records is None) or (vp is not None and (len(vp._forward_hooks) or len(vp._forward_pre_hooks))):  # not capturable
             f = image_features if image_features is not None else (self.encode_images(images) if images is not None else None)
             embeds = self._assemble(lay, self._dev_idx(lay), inputs, f)
             x, _, _, _ = self._prefill(embeds, lens, indices, target, reserve=max_new + 1, last_only=True)
-            self._first_token(st, x, None if fork is None else (target, cache, fork[1], max(lens)))
+            self._first_token(st, x, None if fork is None else (target, cache, fork[1], max(lens)), placed(max(lens)))
             if fork is not None:
                 self._fork_host_mirrors(target, cache, fork[1])
+            if place is not None:
+                self._place_host_mirrors(target, cache, place[2], place[3])
             return None, "eager"
         # ADVICE r3: the instruct predictor's compaction span is baked into the captured plan, and `sig` ignores token values: two
         # equally long multi-turn prompts whose last "USER:" sits elsewhere must not share a graph
@@ -595,6 +601,8 @@ class PrefillEngine:
                self._prefill_knob_key(), self._kv_format_key(cache))  # (a knob toggled at run time must not replay a graph captured under the other setting)
         if fork is not None:  # the graph holds both caches' pointers (_drop_graphs_on looks for either slab's among the key's elements)
             key += (fork[1], target.slab.data_ptr(), target.t_cap, self._kv_format_key(target), self._fork_logits.data_ptr())
+        if place is not None:  # (likewise; the row maps are device tensors made once per pair count, their pointers part of the key)
+            key += ("place", place[2], place[3], place[1][0].data_ptr(), place[1][1].data_ptr(), target.slab.data_ptr(), target.t_cap, self._kv_format_key(target), self._fork_logits.data_ptr())
         ent = self._prefill_graphs.get(key)
         path = "eager" if ent is None else ("graph-capture" if ent["graph"] is None else "graph-replay")
         if ent is None:
@@ -616,7 +624,7 @@ class PrefillEngine:
             else:
                 ent["didx"] = self._dev_idx(lay)
 
-            def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st, target=target, fork=fork):
+            def run(ent=ent, lay=lay, dev_layout=dev_layout, n_feat=n_feat, cache=cache, st=st, target=target, fork=fork, placed=placed):
                 if dev_layout:
                     p_ = ent["plan"]  # the plan's shapes are the bucket's; its device metadata is (re)written here at the true width
                     ops.prompt_layout_into(ent["ids"], n_feat, IMAGE_TOKEN_INDEX, USER_IDS, ent["didx"], w_true=ent["w_true"], n_drop=(p_["n_img"] - p_["k"]) if p_["vision_on"] else 0,
@@ -624,14 +632,15 @@ class PrefillEngine:
                 f = ent["feats"] if ent["feats"] is not None else (self.encode_images(ent["images"]) if ent["images"] is not None else None)
                 emb = self._assemble(lay, ent["didx"], ent["ids"], f)
                 x = self._prefill_run(ent["plan"], emb, target, copy.deepcopy(ent["indices"]), True)
-                self._first_token(st, x, None if fork is None else (target, cache, fork[1], ent["plan"]["max_len"]))
+                self._first_token(st, x, None if fork is None else (target, cache, fork[1], ent["plan"]["max_len"]), placed(ent["plan"]["max_len"]))
 
             ent["run"] = run
             self._prefill_graphs[key] = ent
             if dev_layout:
                 ent["ids"][:, : inputs.shape[1]].copy_(inputs)
                 ent["w_true"].fill_(inputs.shape[1])
-            st.step.zero_(); st.finished.zero_()
+            if place is None or place[2] == 0:
+                st.step.zero_(); st.finished.zero_()
             run()
         else:
             self._prefill_graphs[key] = self._prefill_graphs.pop(key)  # most recently used last
@@ -653,7 +662,8 @@ class PrefillEngine:
                     ent["run"]()
                 ent["graph"] = g_
                 ent["run"] = None
-            st.step.zero_(); st.finished.zero_()
+            if place is None or place[2] == 0:
+                st.step.zero_(); st.finished.zero_()
             ent["graph"].replay()
         p_host = ent["plan"]
         if dev_layout and lay["bucket"] != lay["width"]:  # host mirrors follow the true lengths, not the bucket's
@@ -662,6 +672,8 @@ class PrefillEngine:
         self._prefill_host_update(p_host, target, indices)
         if fork is not None:
             self._fork_host_mirrors(target, cache, fork[1])
+        if place is not None:
+            self._place_host_mirrors(target, cache, place[2], place[3])
         return ent, path
 
     def _unpad_embeds(self, inputs_embeds, attention_mask, input_embeds_indices):

@@ -7,7 +7,7 @@ from typing import Any, Optional, Tuple
 
 import torch
 
-from . import constraints, logits_rules, logprobs, sampling, stopping
+from . import constraints, guidance, logits_rules, logprobs, sampling, stopping
 from .sampling import eos_ids  # the only resolver of eos_token_id; defined in that leaf module because sampling.device_route needs it too
 
 
@@ -75,6 +75,7 @@ class Request:
     streamer: Any = None  # put(tensor) / end(): receives the tokens as they come (stopping.Feed)
     constraint: Any = None  # constraint= / guided_choice= / allowed_token_ids=, compiled (constraints.Table): every row walks it, tokens without an edge are -inf
     allowed_fn: Any = None  # prefix_allowed_tokens_fn=: fn(batch_id, ids_1d) -> the allowed ids, served by the host loop only
+    guidance: Optional[tuple] = None  # guidance_scale= (not None, not 1.0) with negative_prompt_ids= / negative_images=: (scale, cutoff or None) -- classifier-free guidance on paired rows (guidance.py)
 
     @property
     def can_finish(self) -> bool:
@@ -94,8 +95,12 @@ class Request:
 def parse(kwargs, config, sync_every=None, batch=None) -> Request:
     """generate()'s **kwargs -> Request.  Every keyword is validated here, before any device work, in this order: the logits processors, score() with
     processors, the stop sequences and criteria, score() with those, the log-probabilities, what is not built (rejected, not silently ignored: DLL:117-152 forwards **kwargs to HF), num_return_sequences,
-    the constraint (batch: the number of prompts, which a list of automata must match), the sampling parameters."""
+    the constraint (batch: the number of prompts, which a list of automata must match), the sampling parameters; the guidance keywords (guidance.validate) in front
+    of them all."""
     V, eos = config.vocab_size, eos_ids(kwargs, config.eos_token_id)
+    guide = guidance.validate(kwargs)
+    if guide is not None and V > sampling.MAX_VOCAB:
+        raise ValueError(f"guidance_scale takes vocabularies of up to {sampling.MAX_VOCAB} entries (the 64-bit fixed-point masses of its log-probabilities)")
     rules = logits_rules.normalize(kwargs, V, eos)  # (a one-token bad word equal to an EOS id is dropped, as in HF)
     forced = kwargs.get("_score_labels")
     if rules.on and forced is not None:
@@ -123,10 +128,10 @@ def parse(kwargs, config, sync_every=None, batch=None) -> Request:
                    generator=kwargs.get("generator"), want_dict=want_dict, want_scores=want_dict and bool(kwargs.get("output_scores")), want_logits=want_dict and bool(kwargs.get("output_logits")),
                    sync_every=sync_every if kwargs.get("sync_every") is None else int(kwargs["sync_every"]), forced=forced, attention_mask=kwargs.get("attention_mask"),
                    image_features=kwargs.get("image_features"), host_layout=bool(kwargs.get("_host_layout")), route=rt, max_new_tokens=kwargs.get("max_new_tokens"), max_length=kwargs.get("max_length"), n_return=n_return,
-                   stops=stops, criteria=criteria, streamer=streamer, constraint=constraint, allowed_fn=allowed_fn)
+                   stops=stops, criteria=criteria, streamer=streamer, constraint=constraint, allowed_fn=allowed_fn, guidance=guide)
 
 
-def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=None):
+def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=None, negative=None):
     """The plain decoding loop of the host routes.  logits: the first step's fp32 [B, V]; advance(next_ids [B]) -> the next step's, called once per token but the
     last.  Per step, in HF's order: the logits processors on the tokens emitted in this call, temperature, the EOS ban of min_new_tokens, top-k, top-p, then the
     argmax (`greedy`) or a draw with torch's generator; pad behind a row's EOS; stops when every row has finished.  -> (tokens: a list of [B], scores: the
@@ -139,8 +144,11 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
     req.constraint (constraints.Table): every row keeps a state; behind the logits processors and in front of the temperature, constraints.apply leaves only the
     tokens with an edge out of the row's state, and the row's token -- pad for a finished row, as the device appends it -- then moves the state
     (constraints.advance).  req.allowed_fn (prefix_allowed_tokens_fn=): at the same place, every unfinished row is masked to fn(b, the row's tokens emitted in
-    this call, an int64 1-D tensor)."""
+    this call, an int64 1-D tensor).
+    req.guidance with negative = (the negative stream's first logits fp32 [B, V], its advance): in front of everything else guidance.apply turns the two streams'
+    raw logits into the guided scores (HF's order: the first processor); both streams are advanced with the same picked token; `raw` stays the conditional stream's."""
     B, eos = logits.shape[0], list(req.eos)
+    neg_logits, neg_advance = negative if (req.guidance is not None and negative is not None) else (None, None)
     states = None if req.constraint is None else req.constraint.starts(B // req.constraint.n_return)
     finished = torch.zeros(B, dtype=torch.bool, device=logits.device)
     finish_col = torch.full((B,), max_new, dtype=torch.int64, device=logits.device)
@@ -151,6 +159,8 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
         z = logits
         if req.n_lp >= 0:
             raw.append(z.clone())
+        if neg_logits is not None:
+            z = guidance.apply(z, neg_logits, *req.guidance)
         if req.rules.on:
             z = req.rules.apply(z, torch.stack(toks, dim=1) if toks else [[]] * B)
         if states is not None:
@@ -193,6 +203,8 @@ def host_loop(logits, advance, req: Request, max_new: int, greedy: bool, finish=
             break
         if step + 1 < max_new:
             logits = advance(nxt)
+            if neg_logits is not None:
+                neg_logits = neg_advance(nxt)
     if finish is not None:
         finish.append(finish_col.clamp(max=len(toks)))
     if req.streamer is not None:

@@ -371,6 +371,20 @@ int dl_kv_fork(const void* src, void* dst, int64_t src_stride_l, int64_t src_str
                int row_bytes, int src_T_cap, int dst_T_cap, const int32_t* src_lens, int64_t src_lens_stride, int32_t* dst_lens, int64_t dst_lens_stride,
                int max_len, void* stream);
 
+/* ---- length-aware, ROW-MAPPED copy of a KV slab: how a prefill made on a source cache reaches its rows of a wider decode cache (the pairs of a guided
+ * generate(): guidance_scale= with negative_prompt_ids= / negative_images=), and how rows leave such a cache again.  Bytes, strides, row_bytes, the two
+ * length groups, the capacities and max_len are dl_kv_fork's.  For map entry i < n_map with s = src_rows[i] and d = dst_rows[i] (int32, DEVICE memory,
+ * read by the launch): the live span of every (layer, plane, head) of source row s is written to the same offsets of destination row d, and with dst_lens
+ * (may be NULL) dst_lens[g][d] = src_lens[g][s] for both groups.  An entry with s outside [0, B_src) or d outside [0, B_dst) is skipped, never
+ * dereferenced; no other byte of dst is written.  The destination rows of one launch must be distinct (the host checks its maps).  No host sync, no
+ * workspace, no atomics: capturable.  src and dst must not overlap.
+ * DL_ERR_ARG: a NULL src / dst / src_lens / src_rows / dst_rows, n_map / B_src / B_dst / row_bytes / n_kv_heads / n_layers < 1, sparse_layer outside
+ * [0, n_layers], a negative stride, capacity or max_len, more than 65535 (entry, head) pairs. */
+int dl_kv_place(const void* src, void* dst, int64_t src_stride_l, int64_t src_stride_p, int64_t src_stride_b, int64_t src_stride_h, int64_t dst_stride_l,
+                int64_t dst_stride_p, int64_t dst_stride_b, int64_t dst_stride_h, int n_layers, int sparse_layer, int B_src, int B_dst, int n_map,
+                const int32_t* src_rows, const int32_t* dst_rows, int n_kv_heads, int row_bytes, int src_T_cap, int dst_T_cap, const int32_t* src_lens,
+                int64_t src_lens_stride, int32_t* dst_lens, int64_t dst_lens_stride, int max_len, void* stream);
+
 /* ---- prefill compaction of the instruct predictor (DML:2261-2375: `torch.where` on the keep decisions of the last instruct turn + gather/cat)
  * without a device->host copy.  ONE packed sequence of `total` rows [total, H]; rows [span0, span0 + n_span) survive where decision[j] != 0,
  * all other rows always.  h_out [total, H] / pos_out [total] receive the kept rows in order (pos_in NULL: the position is the row index);
@@ -566,6 +580,33 @@ typedef struct dl_stop_table {
   int32_t seq[DL_STOP_MAX_SEQS][1 + DL_STOP_MAX_LEN]; /* a length, then the ids */
 } dl_stop_table;
 int dl_decode_stop(const int64_t* out_ids, int out_cap, int B, const int32_t* step, int32_t* finished, const dl_stop_table* table, void* stream);
+
+/* ---- classifier-free guidance on paired rows (generate(guidance_scale=, negative_prompt_ids= / negative_images=)): HF's
+ * UnbatchedClassifierFreeGuidanceLogitsProcessor / visual contrastive decoding, with the negative prompt as a second row of the same decode step.  Runs in
+ * FRONT of dl_logits_process, dl_logits_constrain and the step-closing launch, which then read `out` in the place of the logits.
+ * logits [2 * n_pairs, V] (bf16 / fp16 / fp32, any row stride >= V, V <= 65536): row p is pair p's conditional row c, row n_pairs + p its negative row u.
+ * Per pair (dynamic_llava_amd/guidance.py states the rule in full and is what the kernel is tested against):
+ *   1. lc(v) = -((m_c - c_v) + lse_c), lu(v) = -((m_u - u_v) + lse_u): m, M and lse of either row exactly as dl_decode_logprobs;
+ *   2. g(v) = s * (lc - lu) + lu: three fp32 operations in this order, each rounded (no fused multiply-add); -inf where c_v or u_v is -inf;
+ *   3. with params->cutoff_on != 0, g(v) = -inf where lc(v) < (-lse_c) + params->log_beta (the conditional argmax is always kept);
+ *   4. out[p, :] = out[n_pairs + p, :] = g.  out: float [2 * n_pairs, V], contiguous, not the logits; the logits are only read.
+ * params: DEVICE memory (one captured graph serves every setting; the host rewrites it between requests).  One workgroup per pair; no workspace, no global
+ * atomics, never synchronises: capturable.  DL_ERR_ARG, and nothing enqueued, for a NULL pointer, n_pairs < 1 or > 32767, V < 1 or > 65536, a row stride
+ * below V, out == logits. */
+typedef struct dl_guide_params {
+  float scale;        /* s */
+  int32_t cutoff_on;  /* 0: step 3 is skipped */
+  float log_beta;     /* log(beta), rounded to fp32 on the host */
+  int32_t reserved[5];
+} dl_guide_params;
+int dl_logits_guide(const void* logits, int logits_dtype, int64_t logits_row_stride, int V, int n_pairs, float* out, const dl_guide_params* params,
+                    void* stream);
+
+/* ---- the pair's one history: runs directly BEHIND the step-closing launch of a guided step (in front of dl_decode_logprobs and dl_decode_stop).  For p <
+ * n_pairs, row n = n_pairs + p takes row p's next_ids, its out_ids slot step[p] - 1 (when that lies in [0, out_cap)) and its finished flag; nothing else is
+ * written -- the negative row's step counter and KV lengths stay its own.  next_ids: int64 [2 * n_pairs]; out_ids: int64 [2 * n_pairs, out_cap]; step,
+ * finished: int32 [2 * n_pairs].  Capturable.  DL_ERR_ARG for a NULL pointer, n_pairs < 1 or out_cap < 1. */
+int dl_pair_follow(int n_pairs, int64_t* next_ids, int64_t* out_ids, int out_cap, const int32_t* step, int32_t* finished, void* stream);
 
 /* ---- decode GEMM for 5..32 rows: Y[M,N] = X[M,K] @ W[N,K]^T (nn.Linear without bias: DML:1011-1013, 1127, 328, 2709), M <=
  * dl_gemm_smallm_max_m().  Weight-streaming like dl_gemv, products on the matrix cores (X resident in LDS, weights HBM -> MFMA
